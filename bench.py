@@ -2,7 +2,18 @@
 """Benchmark: BA LM-iterations/s (+ obs/s) on the C4 scene and all-pairs SIFT
 matching pairs/s on the C3 collection (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up the C4 scene, warms up, times the K steps and prints the
+result line (metric, value, unit, ms_per_step, ...); nothing else.
+--dump-outputs DIR writes what the last timed step computed (the adjusted
+extrinsics, intrinsics and points a caller downloads from the plan, and its
+summary) as DIR/<name>.npy, float64; the scene is seeded, so two builds run
+with the same arguments are comparable array for array.  --full adds every
+other section below to the same line: the Schur roofline, the host-buffer
+solve, the BAL / RADIAL3 / dense-S variants, the C3 matcher, the C5 loop, the
+geometric filter, the CPU baselines and the rocprofv3 counter passes (the
+--no-* switches trim a --full run).
 
 A step is one complete bundle adjustment (sfm_ba_plan_run: Ceres-semantics LM
 from the same initial point to termination) of the C4 scene — 1000 cameras,
@@ -12,10 +23,10 @@ the whole job / wall time (max over ranks).  For N>1 every rank holds one
 landmark block and the reduced camera system is all-reduced over RCCL inside
 libsfmcore (strong scaling: the problem is fixed).
 
-The C3 matcher (500 frames x 4096 x 128-D uint8, exhaustive 124,750 pairs,
-ratio 0.8) runs after the BA steps; pairs are split across ranks.
+With --full, the C3 matcher (500 frames x 4096 x 128-D uint8, exhaustive
+124,750 pairs, ratio 0.8) runs after the BA steps; pairs are split across ranks.
 
-cpu_baseline: the oracle (test infrastructure, CPU restatement of the
+cpu_baseline (--full): the oracle (test infrastructure, CPU restatement of the
 reference Ceres semantics) on a bounded sample, rank 0 at N=1 only.
 """
 import argparse
@@ -622,6 +633,36 @@ def loop_replica_line(r, seconds, images):
     return out
 
 
+def schur_launch_ms(plan, solves):
+    """Mean HIP-event time (ms) and count of every Schur launch but each
+    solve's first (which also forms the point scales), over `solves` separate
+    solves outside the timed region (the timed solves carry no events: an
+    event pair serialises the stream for ~12 us)."""
+    os.environ["SFM_SCHUR_TIME_ALL"] = "1"
+    ms, n = 0.0, 0
+    for _ in range(solves):
+        plan.run()
+        inf = plan.info()
+        ms += inf.schur_ms_total
+        n += inf.schur_launches
+    plan.ctx.synchronize()
+    del os.environ["SFM_SCHUR_TIME_ALL"]
+    return ms / max(n, 1), n
+
+
+def dump_outputs(path, plan, summ):
+    """--dump-outputs: what the last timed step left for its caller, float64."""
+    os.makedirs(path, exist_ok=True)
+    extr, intr, X = plan.download()
+    np.save(os.path.join(path, "extr.npy"), extr)
+    np.save(os.path.join(path, "intr.npy"), intr)
+    np.save(os.path.join(path, "X.npy"), X)
+    np.save(os.path.join(path, "summary.npy"),
+            np.array([summ.iterations, summ.successful_steps, summ.unsuccessful_steps, summ.termination,
+                      summ.initial_cost, summ.final_cost, summ.rmse_initial, summ.rmse_final], np.float64))
+    log(f"outputs: extr {extr.shape}, intr {intr.shape}, X {X.shape}, summary (8,) -> {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -630,6 +671,11 @@ def main():
     # 2-3 % low box to box); only the BA sections use these counts
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (rank 0's plan) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every section beside the headline C4 steps (roofline, variants, matcher, "
+                         "loop, filter, CPU baselines, counter passes); the --no-* switches apply to it")
     ap.add_argument("--n-pt", type=int, default=500_000)
     ap.add_argument("--n-cam", type=int, default=1000)
     ap.add_argument("--match-frames", type=int, default=500)
@@ -772,26 +818,18 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0)
     value = iters / dt
     obs_per_sec = iters * sc["n_obs"] / dt
-    # the roofline's launch time: every Schur launch but each solve's first
-    # (which also forms the point scales), over separate solves after the timed
-    # region (the timed solves carry no events: an event pair serialises the
-    # stream for ~12 us)
-    os.environ["SFM_SCHUR_TIME_ALL"] = "1"
-    schur_ms, schur_n = 0.0, 0
-    for _ in range(max(3, min(args.steps, 10))):
-        plan.run()
-        inf = plan.info()
-        schur_ms += inf.schur_ms_total
-        schur_n += inf.schur_launches
-    ctx.synchronize()
-    del os.environ["SFM_SCHUR_TIME_ALL"]
-    schur_avg_ms = schur_ms / max(schur_n, 1)
+    if args.dump_outputs and rank == 0 and summ is not None:
+        dump_outputs(args.dump_outputs, plan, summ)
+    full = args.full
+    # the roofline's launch time, over separate solves after the timed region
+    schur_avg_ms, schur_n = schur_launch_ms(plan, max(3, min(args.steps, 10))) if full else (0.0, 0)
     flops = info.schur_flops_per_iter
     achieved = flops / (schur_avg_ms * 1e-3) / 1e12 if schur_n else 0.0
     # (iterations per solve printed: a --fake-world shard solves its own
     # problem, whose accept / reject mix differs from the whole scene's)
     log(f"BA: {iters} LM iterations in {dt:.3f}s -> {value:.1f} it/s ({summ.iterations} per solve), rmse "
-        f"{summ.rmse_initial:.4f}->{summ.rmse_final:.4f}, schur avg {schur_avg_ms:.3f} ms")
+        f"{summ.rmse_initial:.4f}->{summ.rmse_final:.4f}"
+        + (f", schur avg {schur_avg_ms:.3f} ms" if full else ""))
     fake_est = None
     if args.fake_world > 1:
         # --fake-world skips every exchange on the device, so its rate leaves
@@ -817,7 +855,7 @@ def main():
     # PCIe-inclusive: one sfm_ba_solve from host buffers (upload, symbolic
     # plan, solve, download) -- reported beside the bench value, never as it
     pcie = None
-    if world == 1:
+    if full and world == 1:
         def host_solve():
             e_h, i_h, x_h = sc["extr"].copy(), sc["intr"].copy(), sc["X"].copy()
             t1 = time.perf_counter()
@@ -837,7 +875,7 @@ def main():
 
     # ---------------- BA, BAL residual model ----------------
     snav = None
-    if not args.no_snavely:
+    if full and not args.no_snavely:
         ssc = c4_scene(args.n_cam, args.n_pt, model=abi.SFM_CAM_SNAVELY)
         splan = api.BAPlan(ctx, ssc["problem"], ssc["extr"], ssc["intr"], ssc["X"])
         for _ in range(args.warmup):
@@ -853,16 +891,7 @@ def main():
         barrier()
         sdt = max_over_ranks(time.perf_counter() - t0)
         # the Schur launch time over separate solves (as for C4 above)
-        os.environ["SFM_SCHUR_TIME_ALL"] = "1"
-        s_ms, s_n = 0.0, 0
-        for _ in range(3):
-            splan.run()
-            inf = splan.info()
-            s_ms += inf.schur_ms_total
-            s_n += inf.schur_launches
-        ctx.synchronize()
-        del os.environ["SFM_SCHUR_TIME_ALL"]
-        s_avg = s_ms / max(s_n, 1)
+        s_avg, s_n = schur_launch_ms(splan, 3)
         s_flops = splan.info().schur_flops_per_iter
         s_ach = s_flops / (s_avg * 1e-3) / 1e12 if s_n else 0.0
         snav = {"metric": "BA LM-iters/sec, SnavelyReprojectionError (BAL) residual model",
@@ -882,7 +911,7 @@ def main():
 
     # ---------------- matching (C3) ----------------
     match = None
-    if not args.no_match:
+    if full and not args.no_match:
         nf, nkp = args.match_frames, 4096
         desc = api.synth_descriptors(nf, nkp)
         off = np.arange(nf + 1, dtype=np.int64) * nkp
@@ -973,11 +1002,11 @@ def main():
 
     # ---------------- incremental loop (C5) ----------------
     loop = loop_fixed = None
-    if world == 1 and rank == 0 and not args.no_loop and args.fake_world <= 1:
+    if full and world == 1 and rank == 0 and not args.no_loop and args.fake_world <= 1:
         loop = bench_loop(ctx, args.loop_images, cpu=not args.no_cpu_baseline)
         loop_fixed = bench_loop(ctx, args.loop_images, cpu=False, fixed_writeback=True, imgs=loop.pop("images"))
         loop_fixed.pop("images", None)
-    elif world > 1 and not args.no_loop:
+    elif full and world > 1 and not args.no_loop:
         # C5 at N > 1: replicas only (DESIGN.md §7 -- the loop is host bound,
         # one image after another).  Every rank runs its own sequence on a
         # one-rank context of its GPU; rank 0 reports the aggregate and every
@@ -996,21 +1025,21 @@ def main():
 
     # ---------------- dense-S stress case ----------------
     dense_s = None
-    if world == 1 and rank == 0 and not args.no_dense and args.fake_world <= 1:
+    if full and world == 1 and rank == 0 and not args.no_dense and args.fake_world <= 1:
         dense_s = bench_dense_s(ctx)
     radial3 = radial3_percam = None
-    if world == 1 and rank == 0 and not args.no_radial3 and args.fake_world <= 1:
+    if full and world == 1 and rank == 0 and not args.no_radial3 and args.fake_world <= 1:
         radial3 = bench_dense_s(ctx, model=abi.SFM_CAM_RADIAL3)
         radial3_percam = bench_radial3_percam(ctx)
 
     # ---------------- geometric filter ----------------
     filt = None
-    if world == 1 and rank == 0 and not args.no_filter and args.fake_world <= 1:
+    if full and world == 1 and rank == 0 and not args.no_filter and args.fake_world <= 1:
         filt = bench_filter(ctx, args.filter_pairs, args.filter_matches, cpu=not args.no_cpu_baseline)
 
     cpu = None
     cpu_match = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline_ba(sc)
             log(f"cpu baseline BA: {cpu['value']:.4f} it/s on {cpu['cores']} threads, "
@@ -1026,7 +1055,8 @@ def main():
     # HBM traffic and MFMA busy of the Schur kernel, measured now (rocprofv3
     # --pmc passes over a child run of the same C4 plan), N = 1 only
     pmc = None
-    if world == 1 and rank == 0 and not args.no_pmc and args.fake_world <= 1:
+    run_pmc = full and world == 1 and rank == 0 and not args.no_pmc and args.fake_world <= 1
+    if run_pmc:
         t1 = time.time()
         pmc = pmc_measure(args)
         log(f"pmc passes: {time.time() - t1:.1f}s -> {pmc}")
@@ -1052,7 +1082,7 @@ def main():
             "algorithmic_flops_per_launch": flops,
             "flops_formula": "sum over points of 3 r (r+1) + 780 k + 30 (r = F rows of the point, "
                              "k = its observations; DESIGN.md §5)"}
-    if world == 1 and rank == 0 and not args.no_pmc and args.fake_world <= 1:
+    if run_pmc:
         t1 = time.time()
         ks = kstats_measure(args)
         log(f"kernel-stats pass: {time.time() - t1:.1f}s -> {ks}")
@@ -1076,7 +1106,7 @@ def main():
             if pmc.get("GRBM_GUI_ACTIVE"):
                 # against the cycles the chip actually ran (GRBM_GUI_ACTIVE sums the 8 XCDs)
                 roof["mfma_busy_clk"] = pmc["SQ_VALU_MFMA_BUSY_CYCLES"] / (1024 * pmc["GRBM_GUI_ACTIVE"] / 8)
-    elif pmc_ok:
+    elif full and pmc_ok:
         roof["traffic"] = pmc_traffic("schur_kernel")
         roof["traffic_source"] = "committed profiles/r*/pmc_summary.json (not measured in this run)"
     if rank == 0:
@@ -1095,7 +1125,8 @@ def main():
             "lm_iterations_per_solve": summ.iterations,
             "fake_world_exchange_estimate": fake_est,
             "rmse_initial": summ.rmse_initial, "rmse_final": summ.rmse_final,
-            "roofline": roof,
+            "full": full,
+            "roofline": roof if full else None,   # its launch times take solves of their own
             "cpu_baseline": cpu,
             "match": match,
             "ba_snavely": snav,

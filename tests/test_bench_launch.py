@@ -59,6 +59,43 @@ def test_loop_replica_line():
 
 
 @pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times the C4 steps and nothing else: every --full section
+    of the line is empty, --steps is the number of timed steps, and
+    --dump-outputs leaves the adjusted parameters of the last step as float64
+    arrays that a second run with the same arguments reproduces."""
+    import numpy as np
+
+    def run(out):
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+                            "--warmup", "1", "--n-cam", "40", "--n-pt", "4000", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        return lines[0], {n: np.load(out / f"{n}.npy") for n in ("extr", "intr", "X", "summary")}
+
+    line, a = run(tmp_path / "a")
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "LM-iters/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0
+    # value = LM iterations of the timed steps / their wall time
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 * 2 - 2 * line["lm_iterations_per_solve"]) < 1e-6
+    for k in ("roofline", "cpu_baseline", "match", "ba_snavely", "ba_pcie_inclusive", "loop",
+              "loop_fixed_writeback", "filter", "ba_dense_s", "ba_radial3", "ba_radial3_percam"):
+        assert line[k] is None, k
+    assert a["extr"].shape == (6 * 40,) and a["X"].shape == (3 * 4000,) and a["summary"].shape == (8,)
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in a.values())
+    assert a["summary"][0] == line["lm_iterations_per_solve"] and a["summary"][7] == line["rmse_final"]
+    assert line["rmse_final"] < line["rmse_initial"]
+    _, b = run(tmp_path / "b")
+    assert np.array_equal(a["summary"][:4], b["summary"][:4])
+    for n in ("extr", "intr", "X"):   # same seeded scene, same solve: equal to rounding of the reductions
+        assert np.allclose(a[n], b[n], rtol=1e-9, atol=1e-9), n
+
+
+@pytest.mark.gpu
 def test_loop_replicas_two_ranks_one_gpu():
     """bench.py's N > 1 loop branch end to end on one GPU: two ranks (the
     RCCL communicator cannot span one device twice, so the BA exchange falls
@@ -73,7 +110,7 @@ def test_loop_replicas_two_ranks_one_gpu():
     env["SFM_BENCH_SAME_DEVICE"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "0", "--n-cam", "40", "--n-pt", "4000",
+           "--gpus", "2", "--full", "--steps", "1", "--warmup", "0", "--n-cam", "40", "--n-pt", "4000",
            "--loop-images", "12", "--allow-host-allreduce", "--no-match", "--no-snavely", "--no-radial3",
            "--no-filter", "--no-dense", "--no-pmc", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)

@@ -7,11 +7,11 @@ TAG=${1:-run}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 900 python -u bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 cd /tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o ba -- \
-    python3 "$GRAFT_REPO_ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-match --no-snavely --no-pmc \
+    python3 "$OLDPWD/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-match --no-snavely --no-pmc \
     > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err" || { tail -30 "$OUT/prof_bench.err"; exit 1; }
 f=$(find "$OUT/prof" -name "*kernel_stats.csv" | head -1)
 cp "$f" "$OUT/kernel_stats.csv"

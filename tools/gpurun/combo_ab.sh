@@ -8,7 +8,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 timeout -k 10 600 python -u -m pytest tests/test_ba_gpu.py tests/test_headline_gpu.py tests/test_radial3.py tests/test_snavely.py tests/test_match_gpu.py -m gpu -x -q --timeout 300 --timeout-method thread > "$OUT/tests.log" 2>&1 || { tail -40 "$OUT/tests.log"; exit 1; }
 tail -1 "$OUT/tests.log"
-ARGS="--steps 20 --no-match --no-snavely --no-loop --no-pmc --no-filter --no-dense --no-radial3 --no-cpu-baseline"
+ARGS="--full --steps 20 --no-match --no-snavely --no-loop --no-pmc --no-filter --no-dense --no-radial3 --no-cpu-baseline"
 for rep in 1 2; do
 for L in $2; do
     export SFMCORE_LIB=$GRAFT_REPO_ROOT/$L
@@ -16,7 +16,7 @@ for L in $2; do
     echo "$L: $r" | tee -a "$OUT/ab.txt"
 done
 done
-MARGS="--steps 2 --no-snavely --no-loop --no-pmc --no-filter --no-dense --no-radial3 --no-cpu-baseline --n-pt 20000 --n-cam 100"
+MARGS="--full --steps 2 --no-snavely --no-loop --no-pmc --no-filter --no-dense --no-radial3 --no-cpu-baseline --n-pt 20000 --n-cam 100"
 for rep in 1 2; do
 for L in $3; do
     export SFMCORE_LIB=$GRAFT_REPO_ROOT/$L

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -q --timeout 400 --timeout-method thread > "$OUT/tests.log" 2>&1 || { tail -40 "$OUT/tests.log"; exit 1; }
 tail -1 "$OUT/tests.log"
-ARGS="--no-match --no-snavely --no-loop --no-pmc --no-filter --no-cpu-baseline"
+ARGS="--full --no-match --no-snavely --no-loop --no-pmc --no-filter --no-cpu-baseline"
 timeout -k 10 600 python -u bench.py --steps 10 $ARGS > "$OUT/c4.json" 2> "$OUT/c4.err" || { tail -20 "$OUT/c4.err"; exit 1; }
 grep -E "^\[bench\] (BA|loop)" "$OUT/c4.err"
 ARGS="$ARGS --no-dense --no-radial3"

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 TAG=${1:-final}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 bash tools/gpurun/bench_prof.sh "$TAG"
-ARGS="--no-match --no-snavely --no-loop --no-pmc --no-filter --no-cpu-baseline --no-dense --no-radial3"
+ARGS="--full --no-match --no-snavely --no-loop --no-pmc --no-filter --no-cpu-baseline --no-dense --no-radial3"
 for rep in 1 2; do
 timeout -k 10 300 python -u bench.py --steps 20 $ARGS 2>&1 >/dev/null | grep "^\[bench\] BA:" | sed "s/^/N1 /" | tee -a "$OUT/fake8.txt"
 timeout -k 10 300 python -u bench.py --fake-world 8 --steps 20 $ARGS 2>&1 >/dev/null | grep "^\[bench\] BA:" | sed "s/^/rank0-of-8 /" | tee -a "$OUT/fake8.txt"

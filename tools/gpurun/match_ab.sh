@@ -3,7 +3,7 @@
 set -e
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
-ARGS="--no-snavely --no-loop --no-pmc --no-filter --no-dense --no-radial3 --no-cpu-baseline --n-pt 20000 --n-cam 100"
+ARGS="--full --no-snavely --no-loop --no-pmc --no-filter --no-dense --no-radial3 --no-cpu-baseline --n-pt 20000 --n-cam 100"
 OUT=$GRAFT_REPO_ROOT/gpurun_out/mab
 mkdir -p "$OUT"
 for L in "$@"; do

@@ -2,7 +2,7 @@
 #   tools/gpurun/model_ab.sh lib1 lib2 ...   ("base" = the in-tree build)
 set -e
 cd "$GRAFT_REPO_ROOT"
-ARGS="--steps 20 --no-match --no-loop --no-pmc --no-filter --no-dense --no-cpu-baseline"
+ARGS="--full --steps 20 --no-match --no-loop --no-pmc --no-filter --no-dense --no-cpu-baseline"
 for rep in 1 2; do
 for L in "$@"; do
     if [ "$L" = base ]; then unset SFMCORE_LIB; else export SFMCORE_LIB=$GRAFT_REPO_ROOT/$L; fi

@@ -13,7 +13,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
     > "$OUT/gputests.log" 2>&1 || { tail -40 "$OUT/gputests.log"; exit 1; }
 tail -2 "$OUT/gputests.log"
 fi
-ARGS="--no-match --no-snavely --no-loop --no-pmc --no-filter --no-dense --no-radial3 --no-cpu-baseline"
+ARGS="--full --no-match --no-snavely --no-loop --no-pmc --no-filter --no-dense --no-radial3 --no-cpu-baseline"
 SFM_BCR_STAMPS=1 timeout -k 10 300 python -u bench.py --steps 5 $ARGS > "$OUT/c4_stamps.json" 2> "$OUT/c4_stamps.err" \
     || { tail -20 "$OUT/c4_stamps.err"; exit 1; }
 grep -E "^\[bench\] BA|bcr stamps" "$OUT/c4_stamps.err" | tail -3

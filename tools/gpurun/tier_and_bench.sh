@@ -12,5 +12,5 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v -s --timeout 400 --tim
 tail -2 "$OUT/gputests.log"
 grep -E "fixed_writeback=" "$OUT/gputests.log" || true
 fi
-timeout -k 10 900 python -u bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+timeout -k 10 900 python -u bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
 grep "^\[bench\]" "$OUT/bench.err" | tail -25
