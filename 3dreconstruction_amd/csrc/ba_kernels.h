@@ -28,6 +28,19 @@ constexpr double kSolveWaitTimeout = 2.0;
 constexpr int kScSumBegin = 0, kScSumEnd = 5, kScMaxBegin = 5, kScMaxEnd = 10;
 constexpr int kPartT = 5;  // per step block: model acc, cand cost, step norm^2, step bad, cand bad
 
+// The long targets of one term list (sum terms or product terms): a target
+// whose list is longer than the list's threshold is summed in kReduceSeg-term
+// segments, one workgroup each (pass 1, partials into part), which pass 2 adds
+// in segment order.
+struct LongList {
+    int32_t n;                  // long targets
+    int32_t n_seg;              // segments of all of them
+    const int32_t* targets;     // [n] target ids
+    const int32_t* seg_off;     // [n + 1] segment range of each long target
+    const int32_t* seg;         // [n_seg][2] (long index, first term)
+    double* part;               // [n_seg][36] segment partial sums
+};
+
 struct DevProblem {
     int32_t n_img, n_intr, n_spt, n_sobs, n_chunk, ncam, nintr, D;
     int32_t n_group;                // tile groups (one Schur workgroup and one tile each)
@@ -71,13 +84,8 @@ struct DevProblem {
     const FlatTerm* terms;
     const double* src;              // contiguous [tiles | U | Ub | Ucn] the terms index
     int32_t n_targets;
-    int32_t n_long;                 // targets with > reduce_long_threshold() terms
-    const int32_t* long_targets;    // [n_long] target ids
-    int32_t n_lseg;                 // kReduceSeg-term segments of the long targets
-    const int32_t* lseg_off;        // [n_long+1] segment ranges per long target
-    const int32_t* lseg;            // [n_lseg][2] (long index, first term)
-    double* lpart;                  // [n_lseg][36] segment partial sums
-    unsigned* lcount;               // [n_long] segments done this launch (the last one combines; reset by it)
+    LongList lsum;                  // targets with > reduce_long_threshold() sum terms
+    unsigned* lcount;               // [lsum.n] segments done this launch (the last one combines; reset by it)
     // general points (ba_plan.h): blocks, Z layout, product terms
     const int32_t* gblk_off;        // [n_gpt+1]
     const int32_t* gblk_col;        // F column of each block
@@ -90,12 +98,7 @@ struct DevProblem {
     const int32_t* zlong;           // [n_zlong] general point
     const PTerm* pterms;
     double* Z;                      // general points' eliminated rows, w after each point's blocks
-    int32_t n_plong;                // targets with > preduce_long_threshold() product terms
-    const int32_t* plong_targets;   // [n_plong] target ids
-    int32_t n_plseg;                // kReduceSeg-term segments of their product-term lists
-    const int32_t* plseg_off;       // [n_plong+1]
-    const int32_t* plseg;           // [n_plseg][2] (long index, first product term)
-    double* plpart;                 // [n_plseg][36]
+    LongList lprod;                 // targets with > preduce_long_threshold() product terms
     // state
     double* scaleE;     // [3*n_spt]
     double* scaleF;     // [nF]

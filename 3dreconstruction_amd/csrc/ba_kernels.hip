@@ -1268,8 +1268,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(DevProblem P, int vectors_o
 // the partials in segment order -- the same sum as reduce_long_kernel)
 template <bool FUSED>
 __device__ __forceinline__ void reduce_segment(const DevProblem& P, int vectors_only, int sg) {
-    const int j = P.lseg[2 * sg], k0 = P.lseg[2 * sg + 1];
-    const ReduceTarget T = P.targets[P.long_targets[j]];
+    const int j = P.lsum.seg[2 * sg], k0 = P.lsum.seg[2 * sg + 1];
+    const ReduceTarget T = P.targets[P.lsum.targets[j]];
     if (skip_kind(T.dst_kind, vectors_only)) return;   // (uniform over the workgroup)
     // each wave a quarter of the segment, in G = 64 / E lane groups of the
     // target's E elements (as reduce_kernel); partials added in (wave, group)
@@ -1289,15 +1289,15 @@ __device__ __forceinline__ void reduce_segment(const DevProblem& P, int vectors_
         double tot = 0.0;
         for (int w = 0; w < 4; ++w)
             for (int q = 0; q < G; ++q) tot += part[w][q * E + t];
-        if (FUSED) st_wt64(P.lpart + (size_t)sg * 36 + t, tot);
-        else P.lpart[(size_t)sg * 36 + t] = tot;
+        if (FUSED) st_wt64(P.lsum.part + (size_t)sg * 36 + t, tot);
+        else P.lsum.part[(size_t)sg * 36 + t] = tot;
     }
     if (!FUSED) return;
     // the partial is drained before the ticket; the last arriver reads every
     // partial of the target write-through (no fences: the counter form)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    const int s0 = P.lseg_off[j], s1 = P.lseg_off[j + 1];
+    const int s0 = P.lsum.seg_off[j], s1 = P.lsum.seg_off[j + 1];
     if (threadIdx.x == 0)
         last = __hip_atomic_fetch_add((gu32_t*)(P.lcount + j), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
                (unsigned)(s1 - s0 - 1);
@@ -1307,7 +1307,7 @@ __device__ __forceinline__ void reduce_segment(const DevProblem& P, int vectors_
         const int e = threadIdx.x;
         double t = 0.0;
 #pragma unroll 8
-        for (int q = s0; q < s1; ++q) t += ld_wt64(P.lpart + (size_t)q * 36 + e);
+        for (int q = s0; q < s1; ++q) t += ld_wt64(P.lsum.part + (size_t)q * 36 + e);
         const int r = e / T.cols, cc = e % T.cols;
         target_base(P, T.dst_kind)[T.dst + (T.cols == 1 ? r : r * T.ld + cc)] = t;
     }
@@ -1319,18 +1319,24 @@ __global__ __launch_bounds__(256) void reduce_seg_kernel(DevProblem P, int vecto
     reduce_segment<false>(P, vectors_only, blockIdx.x);
 }
 
-// pass 2: segment partials added in segment order
+// pass 2 of a long list: segment partials added in segment order; the sum
+// terms' total is the target's value, the product terms' (SUBTRACT, never in
+// a vectors-only pass) is subtracted from it
+template <bool SUBTRACT>
 __global__ __launch_bounds__(64) void reduce_long_kernel(DevProblem P, int vectors_only) {
+    const LongList& L = SUBTRACT ? P.lprod : P.lsum;
     const int j = blockIdx.x;
-    const ReduceTarget T = P.targets[P.long_targets[j]];
-    if (skip_kind(T.dst_kind, vectors_only)) return;
+    const ReduceTarget T = P.targets[L.targets[j]];
+    if (!SUBTRACT && skip_kind(T.dst_kind, vectors_only)) return;
     const int E = T.rows * T.cols, e = threadIdx.x;
     if (e >= E) return;
     double t = 0.0;
 #pragma unroll 8
-    for (int sg = P.lseg_off[j]; sg < P.lseg_off[j + 1]; ++sg) t += P.lpart[(size_t)sg * 36 + e];
+    for (int sg = L.seg_off[j]; sg < L.seg_off[j + 1]; ++sg) t += L.part[(size_t)sg * 36 + e];
     const int r = e / T.cols, cc = e % T.cols;
-    target_base(P, T.dst_kind)[T.dst + (T.cols == 1 ? r : r * T.ld + cc)] = t;
+    double* dst = target_base(P, T.dst_kind) + T.dst + (T.cols == 1 ? r : (int64_t)r * T.ld + cc);
+    if (SUBTRACT) *dst -= t;
+    else *dst = t;
 }
 
 // ---------------------------------------------------------------------------
@@ -2178,7 +2184,7 @@ __global__ __launch_bounds__(64) void zbatch_kernel(DevProblem P, const CamPre* 
 // target, one lane per element; runs after reduce_kernel has written the sum
 // terms.
 // Lists longer than this (the intrinsics arrow and corner collect one term
-// per general point) go through preduce_seg_kernel + preduce_long_kernel.
+// per general point) go through preduce_seg_kernel + reduce_long_kernel<true>.
 constexpr int kLongPTerms = 64;
 
 // sum over the product terms q = qa + g, qa + g + G, ... < qb of
@@ -2359,8 +2365,8 @@ __global__ __launch_bounds__(256) void preduce_kernel(DevProblem P) {
 // E elements); the partials added in (wave, group) order, fixed.
 __global__ __launch_bounds__(256) void preduce_seg_kernel(DevProblem P) {
     const int sg = blockIdx.x;
-    const int j = P.plseg[2 * sg], k0 = P.plseg[2 * sg + 1];
-    const ReduceTarget T = P.targets[P.plong_targets[j]];
+    const int j = P.lprod.seg[2 * sg], k0 = P.lprod.seg[2 * sg + 1];
+    const ReduceTarget T = P.targets[P.lprod.targets[j]];
     const int E = T.rows * T.cols;
     const bool vec = T.cols == 1;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2383,22 +2389,12 @@ __global__ __launch_bounds__(256) void preduce_seg_kernel(DevProblem P) {
         double tot = 0.0;
         for (int w = 0; w < 4; ++w)
             for (int k = 0; k < pl.G; ++k) tot += (second ? part1[w] : part[w])[k * pl.E2 + e2];
-        P.plpart[(size_t)sg * 36 + t] = tot;
+        P.lprod.part[(size_t)sg * 36 + t] = tot;
     }
 }
 
-// pass 2: segment partials added in segment order, subtracted from the target
-__global__ __launch_bounds__(64) void preduce_long_kernel(DevProblem P) {
-    const int j = blockIdx.x;
-    const ReduceTarget T = P.targets[P.plong_targets[j]];
-    const int E = T.rows * T.cols, e = threadIdx.x;
-    if (e >= E) return;
-    double t = 0.0;
-#pragma unroll 8
-    for (int sg = P.plseg_off[j]; sg < P.plseg_off[j + 1]; ++sg) t += P.plpart[(size_t)sg * 36 + e];
-    const int r = e / T.cols, cc = e % T.cols;
-    target_base(P, T.dst_kind)[T.dst + (T.cols == 1 ? r : (int64_t)r * T.ld + cc)] -= t;
-}
+// (pass 2: reduce_long_kernel<true>, segment partials added in segment order
+// and subtracted from the target)
 
 // Step for general points: one thread per point, the same arithmetic as
 // step_kernel with cameras and column scales read from global memory.
@@ -2666,16 +2662,6 @@ void ba_campre(const double* extr, int n_img, CamPre* out, hipStream_t s) {
 
 // the residual model is a template parameter of every kernel that linearises
 // (chunk tiles carry the model's intrinsics width: 4, RADIAL3 6)
-#define SFM_BY_MODEL(P, CALL)                                  \
-    do {                                                       \
-        if ((P).cam_model == SFM_CAM_SNAVELY) {                \
-            constexpr int CM = SFM_CAM_SNAVELY;                \
-            CALL;                                              \
-        } else {                                               \
-            constexpr int CM = SFM_CAM_PINHOLE;                \
-            CALL;                                              \
-        }                                                      \
-    } while (0)
 #define SFM_BY_MODEL_ALL(P, CALL)                              \
     do {                                                       \
         if ((P).cam_model == SFM_CAM_RADIAL3) {                \
@@ -2731,50 +2717,42 @@ void ba_fscale(const DevProblem& P, hipStream_t s) {
     SFM_HIP(hipGetLastError());
 }
 
+// a run-time flag as a compile-time tag (as ba_step's lanes-per-point tag)
+template <class F>
+void by_flag(bool v, F&& fn) {
+    if (v) fn(std::true_type{});
+    else fn(std::false_type{});
+}
+
 void ba_schur(const DevProblem& P, const CamPre* cp, const double* intr, const double* X, double radius,
               hipStream_t s, unsigned long long* stamps, bool scale_e) {
-    if (P.n_zbatch > 0) {
-        if (scale_e)
-            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((zbatch_kernel<CM, true>), dim3(P.n_zbatch), dim3(64), 0, s, P, cp,
+    by_flag(scale_e, [&](auto tag) {
+        constexpr bool SE = decltype(tag)::value;
+        if (P.n_zbatch > 0) {
+            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((zbatch_kernel<CM, SE>), dim3(P.n_zbatch), dim3(64), 0, s, P, cp,
                                                    intr, X, radius));
-        else
-            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((zbatch_kernel<CM, false>), dim3(P.n_zbatch), dim3(64), 0, s, P,
-                                                   cp, intr, X, radius));
-        SFM_HIP(hipGetLastError());
-    }
-    if (P.n_zlong > 0) {
-        const size_t lds = (64 * kZStage + (size_t)P.gz_max) * sizeof(double);
-        if (scale_e)
+            SFM_HIP(hipGetLastError());
+        }
+        if (P.n_zlong > 0) {
+            const size_t lds = (64 * kZStage + (size_t)P.gz_max) * sizeof(double);
             SFM_BY_MODEL_ALL(P, {
-                if (lds > 64 * 1024) set_dyn_lds((const void*)zpoint_kernel<CM, true>, lds);
-                hipLaunchKernelGGL((zpoint_kernel<CM, true>), dim3(P.n_zlong), dim3(64), lds, s, P, cp, intr, X, radius);
+                if (lds > 64 * 1024) set_dyn_lds((const void*)zpoint_kernel<CM, SE>, lds);
+                hipLaunchKernelGGL((zpoint_kernel<CM, SE>), dim3(P.n_zlong), dim3(64), lds, s, P, cp, intr, X, radius);
             });
+            SFM_HIP(hipGetLastError());
+        }
+        if (P.n_group <= 0) return;
+        // 64-row tiles: batches of schur4_pts(CM) points (ba_types.h) at 8 waves
+        // per CU (6-point batches' LDS allows 7, and measured 9% slower)
+        const dim3 grid(P.n_group), block(64 * schur_group(P.tile_nt));
+        if (P.tile_nt == 4)
+            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((schur_kernel<CM, 4, schur4_pts(CM), schur4_obs(CM), SE>), grid, block,
+                                                   0, s, P, cp, intr, X, radius, stamps));
         else
-            SFM_BY_MODEL_ALL(P, {
-                if (lds > 64 * 1024) set_dyn_lds((const void*)zpoint_kernel<CM, false>, lds);
-                hipLaunchKernelGGL((zpoint_kernel<CM, false>), dim3(P.n_zlong), dim3(64), lds, s, P, cp, intr, X, radius);
-            });
+            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((schur_kernel<CM, 5, kSubPts, kSubObs, SE>), grid, block, 0, s, P, cp,
+                                                   intr, X, radius, stamps));
         SFM_HIP(hipGetLastError());
-    }
-    if (P.n_group <= 0) return;
-    // 64-row tiles: batches of schur4_pts(CM) points (ba_types.h) at 8 waves
-    // per CU (6-point batches' LDS allows 7, and measured 9% slower)
-    if (P.tile_nt == 4) {
-        if (scale_e)
-            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((schur_kernel<CM, 4, schur4_pts(CM), schur4_obs(CM), true>),
-                                               dim3(P.n_group), dim3(64 * schur_group(P.tile_nt)), 0, s, P, cp, intr, X, radius, stamps));
-        else
-            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((schur_kernel<CM, 4, schur4_pts(CM), schur4_obs(CM)>),
-                                               dim3(P.n_group), dim3(64 * schur_group(P.tile_nt)), 0, s, P, cp, intr, X, radius, stamps));
-    } else {
-        if (scale_e)
-            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((schur_kernel<CM, 5, kSubPts, kSubObs, true>),
-                                               dim3(P.n_group), dim3(64 * schur_group(P.tile_nt)), 0, s, P, cp, intr, X, radius, stamps));
-        else
-            SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((schur_kernel<CM, 5, kSubPts, kSubObs>), dim3(P.n_group),
-                                               dim3(64 * schur_group(P.tile_nt)), 0, s, P, cp, intr, X, radius, stamps));
-    }
-    SFM_HIP(hipGetLastError());
+    });
 }
 
 void ba_reduce(const DevProblem& P, bool vectors_only, hipStream_t s) {
@@ -2782,28 +2760,28 @@ void ba_reduce(const DevProblem& P, bool vectors_only, hipStream_t s) {
     const int per_block = 4 / P.red_waves, nb = (P.n_targets + per_block - 1) / per_block;
     const bool split = P.red_split != 0;   // SFM_CTX_BA_SPLIT_REDUCE: three launches
     const int nz = (P.n_zero + 15) / 16;   // zero-list workgroups, last in the grid
-    if (P.n_long > 0 && !split) {
-        hipLaunchKernelGGL(reduce_kernel<true>, dim3(nb + P.n_lseg + nz), dim3(256), 0, s, P, vectors_only ? 1 : 0,
-                           nb, nb + P.n_lseg);
+    if (P.lsum.n > 0 && !split) {
+        hipLaunchKernelGGL(reduce_kernel<true>, dim3(nb + P.lsum.n_seg + nz), dim3(256), 0, s, P, vectors_only ? 1 : 0,
+                           nb, nb + P.lsum.n_seg);
         SFM_HIP(hipGetLastError());
     } else {
         hipLaunchKernelGGL(reduce_kernel<false>, dim3(nb + nz), dim3(256), 0, s, P, vectors_only ? 1 : 0, nb, nb);
         SFM_HIP(hipGetLastError());
     }
-    if (P.n_long > 0 && split) {
-        hipLaunchKernelGGL(reduce_seg_kernel, dim3(P.n_lseg), dim3(256), 0, s, P, vectors_only ? 1 : 0);
+    if (P.lsum.n > 0 && split) {
+        hipLaunchKernelGGL(reduce_seg_kernel, dim3(P.lsum.n_seg), dim3(256), 0, s, P, vectors_only ? 1 : 0);
         SFM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(reduce_long_kernel, dim3(P.n_long), dim3(64), 0, s, P, vectors_only ? 1 : 0);
+        hipLaunchKernelGGL(reduce_long_kernel<false>, dim3(P.lsum.n), dim3(64), 0, s, P, vectors_only ? 1 : 0);
         SFM_HIP(hipGetLastError());
     }
     // product terms (general points) land on the matrix and rhs targets
     if (P.n_gpt > 0 && !vectors_only) {
         hipLaunchKernelGGL(preduce_kernel, dim3((P.n_targets + 3) / 4), dim3(256), 0, s, P);
         SFM_HIP(hipGetLastError());
-        if (P.n_plong > 0) {
-            hipLaunchKernelGGL(preduce_seg_kernel, dim3(P.n_plseg), dim3(256), 0, s, P);
+        if (P.lprod.n > 0) {
+            hipLaunchKernelGGL(preduce_seg_kernel, dim3(P.lprod.n_seg), dim3(256), 0, s, P);
             SFM_HIP(hipGetLastError());
-            hipLaunchKernelGGL(preduce_long_kernel, dim3(P.n_plong), dim3(64), 0, s, P);
+            hipLaunchKernelGGL(reduce_long_kernel<true>, dim3(P.lprod.n), dim3(64), 0, s, P, 0);
             SFM_HIP(hipGetLastError());
         }
     }

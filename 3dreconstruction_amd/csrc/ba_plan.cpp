@@ -1103,7 +1103,654 @@ void plan_points(const sfm_ba_problem& P, BAHostPlan& pl, const PlanOpts& opts, 
     tm.mark("image_csr");
 }
 
-void build_reduce_plan(const sfm_ba_problem& P, BAHostPlan& pl, PhaseTimer& tm, BAHostPlan* seed = nullptr);
+// ---- reduce plan -----------------------------------------------------------
+// Every matrix block (a, b), a >= b in F-block order (cameras, then
+// intrinsics), is a target summing its terms in a fixed order: sum terms
+// (image Gram slices in image order, then chunk tile sub-blocks in tile
+// group order) and product terms (general points in order); vectors (rhs,
+// bF, cnF) likewise per block -- so every sum is bit-reproducible.  Both
+// lists are laid out target after target.  They are built by a counting
+// scatter over F-block rows, without materialising or sorting (key, term)
+// lists: per-row term counts first (one pass over the sources, O(blocks)),
+// which fix every row's first position; then each host thread takes a
+// range of rows, counts its targets' terms, and writes every term of its
+// rows straight to its final place, visiting the sources in their order.
+//
+// The order of the sources and the rules of which (fa, fb) pairs are terms
+// are written once, in the walks (walk_matrix, walk_vectors): the count pass
+// and the write pass of a row range are the same walk with another visitor.
+// After the write pass every cursor must stand at its target's end
+// (matrix_segment, vector_segment), so a count that disagrees with the
+// writes fails the plan instead of running into the neighbouring target.
+//
+// The stages run in the order of build_reduce_plan below, over this state.
+struct ReducePlanner {
+    const sfm_ba_problem& P;
+    BAHostPlan& pl;
+    PhaseTimer& tm;
+    BAHostPlan* const seed;
+    const int world;
+    const int32_t nFB, ncam, nintr, D;
+    const int Dp;
+    const int32_t gseg, ngrp;
+    const bool band;
+    // Terms are stored resolved against the solver's one source buffer
+    const SourceLayout lay;
+
+    // the images that contribute Gram slices: (image, camera block, F block of its intrinsics)
+    struct ImgSrc {
+        int32_t img, cb, fq;
+    };
+    std::vector<ImgSrc> isrc;
+    // F-block range of every tile group and general point (rows they write)
+    std::vector<int32_t> g_lo, g_hi, p_lo, p_hi;
+    // F block of every general-point block (pfb) and tile-group slot (gfb)
+    std::vector<int32_t> pfb, gfb;
+    // per-row counts and first positions: matrix sum / product terms, rhs sum /
+    // product terms, image slices (bF and cnF)
+    enum { kMc, kMp, kVc, kVp, kVb, kNC };
+    std::vector<int64_t> rc, base;
+    int64_t n_mc = 0, n_mp = 0, n_vc = 0, n_vp = 0, n_vb = 0, n_terms = 0, n_pterms = 0;
+    int32_t f0 = 0;       // grown plans: the matrix rows before f0 are the seed's
+    int64_t t_keep = 0;   // the seed's targets kept
+    std::vector<int32_t> cut;   // row ranges of the matrix rows f0..
+    std::vector<std::vector<ReduceTarget>> seg_targets;
+    std::vector<std::vector<int32_t>> seg_rows;   // each row's first target within its segment
+
+    ReducePlanner(const sfm_ba_problem& P_, BAHostPlan& pl_, PhaseTimer& tm_, BAHostPlan* seed_)
+        : P(P_), pl(pl_), tm(tm_), seed(seed_), world(pl_.world), nFB(pl_.nFB), ncam(pl_.ncam), nintr(pl_.nintr),
+          D(pl_.D), Dp(pl_.D + 1), gseg(pl_.gram_seg), ngrp((int32_t)pl_.n_group()), band(!pl_.dense),
+          lay(pl_.n_group(), P_.n_img, pl_.iw) {}
+
+    // ---- index helpers -----------------------------------------------------
+    int32_t fb_of_col(int64_t col) const {
+        return col < pl.nb ? (int32_t)(col / 6) : (int32_t)(ncam + (col - pl.nb) / pl.iw);
+    }
+    int64_t col_of_fb(int32_t b) const { return b < ncam ? 6LL * b : pl.nb + (int64_t)pl.iw * (b - ncam); }
+    int32_t size_of_fb(int32_t b) const { return b < ncam ? 6 : pl.iw; }
+    const ChunkDesc& grp(int32_t c) const { return pl.chunks[pl.group_off[c]]; }
+    int64_t& RC(int w, int32_t f) { return rc[(size_t)w * (nFB + 1) + f]; }
+    int64_t& BS(int w, int32_t f) { return base[(size_t)w * (nFB + 1) + f]; }
+    // band: a corner block (k, l), k < l, is stored too, as the transpose of
+    // (l, k): terms of an off-diagonal corner key go to two targets
+    bool twice(int32_t fa, int32_t fb) const { return band && fb >= ncam && fb != fa; }
+    // a tile group's window can be wider than the band: its slot pairs
+    // further apart than D are structurally zero (no point sees both) and
+    // have no target
+    bool held(int32_t fa, int32_t fb) const { return !band || fa >= ncam || fa - fb <= D; }
+
+    FlatTerm flat(const ReduceTerm& q, bool vec) const {
+        FlatTerm f{};
+        f.sign = q.sign;
+        f.mode = kFlatRows;
+        const int64_t fw = lay.fw;
+        switch (q.kind) {
+            case kSrcTile: {
+                // slot blocks occupy disjoint tile rows, so a block of two
+                // slots is wholly below or wholly above the diagonal
+                const int64_t tile0 = (int64_t)q.index * kTileR * kTileR;
+                if (vec || q.roff > q.coff) {
+                    f.off = tile0 + q.roff * kTileR + q.coff;
+                    f.rs = vec ? 1 : kTileR;
+                } else if (q.roff < q.coff) {
+                    f.off = tile0 + q.coff * kTileR + q.roff;
+                    f.rs = 1;
+                    f.mode = kFlatTrans;
+                } else {   // rs = the origin's offset within the tile
+                    f.off = tile0 + q.roff * kTileR + q.coff;
+                    f.rs = (int16_t)(q.roff * kTileR + q.coff);
+                    f.mode = kFlatSym;
+                }
+                break;
+            }
+            case kSrcU:
+                f.off = lay.o_u + q.index * fw * fw + q.roff * fw + q.coff;
+                f.rs = (int16_t)fw;
+                break;
+            case kSrcUb:
+                f.off = lay.o_ub + q.index * fw + q.roff;
+                f.rs = 1;
+                break;
+            default:
+                f.off = lay.o_ucn + q.index * fw + q.roff;
+                f.rs = 1;
+                break;
+        }
+        return f;
+    }
+
+    // matrix targets of row fa: band -- the band blocks (fa, fa-d), d from
+    // min(D, fa) down to 0; an intrinsics row ncam+m: the arrow (m, i) for
+    // every camera, then per corner column l <= m the transposed (l, m) (l <
+    // m) and (m, l) -- the order a stable sort of the targets by key gives.
+    // Dense: every block (fa, fb <= fa) that receives a term.
+    int64_t row_slots(int32_t f) const {
+        if (!band) return (int64_t)f + 1;
+        return f < ncam ? std::min(D, f) + 1 : ncam + 2 * (f - ncam) + 1;
+    }
+    // slot of (fa, fb) within row fa; a transposed twin sits at slot - 1
+    int64_t slot_of(int32_t fa, int32_t fb) const {
+        if (!band) return fb;
+        if (fa < ncam) return fb - (fa - std::min(D, fa));
+        if (fb < ncam) return fb;
+        return ncam + 2 * (fb - ncam) + (fb != fa ? 1 : 0);   // the (fa, fb) target; its twin precedes it
+    }
+    int64_t dense_dst(int32_t fa, int32_t fb) const { return col_of_fb(fa) * pl.nF + col_of_fb(fb); }
+    ReduceTarget make_target(int32_t fa, int64_t s) const {
+        ReduceTarget t{};
+        if (!band) {
+            const int32_t fb = (int32_t)s;
+            t.dst = dense_dst(fa, fb);
+            t.dst_kind = kDstDense;
+            t.rows = size_of_fb(fa); t.cols = size_of_fb(fb); t.ld = (int32_t)pl.nF;
+        } else if (fa < ncam) {
+            const int d = std::min(D, fa) - (int)s;
+            t.dst = ((int64_t)fa * Dp + d) * 36;
+            t.dst_kind = kDstBand;
+            t.rows = 6; t.cols = 6; t.ld = 6;
+        } else if (s < ncam) {
+            t.dst = ((int64_t)(fa - ncam) * ncam + s) * 6 * pl.iw;
+            t.dst_kind = kDstArrow;
+            t.rows = pl.iw; t.cols = 6; t.ld = 6;
+        } else {
+            const int m = fa - ncam, u = (int)(s - ncam), lp = u / 2;
+            const bool trans = (u & 1) == 0 && lp < m;
+            const int k = trans ? lp : m, l = trans ? m : lp;
+            t.dst = ((int64_t)k * nintr + l) * pl.iw * pl.iw;
+            t.dst_kind = kDstCorner;
+            t.rows = pl.iw; t.cols = pl.iw; t.ld = pl.iw;
+        }
+        return t;
+    }
+    // row ranges of about equal work (terms, plus the row's targets)
+    std::vector<int32_t> row_cuts(int32_t fa0, bool matrix) {
+        std::vector<int32_t> c{fa0};
+        int64_t tot = 0;
+        std::vector<int64_t> w(nFB);
+        for (int32_t f = fa0; f < nFB; ++f) {
+            w[f] = matrix ? RC(kMc, f) + RC(kMp, f) + row_slots(f) : RC(kVc, f) + RC(kVp, f) + 2 * RC(kVb, f);
+            tot += w[f];
+        }
+        const int nt = tot < 65536 ? 1 : std::min<int>(PlanPool::width(), std::max(1, nFB - fa0));
+        int64_t acc = 0;
+        for (int32_t f = fa0; f < nFB; ++f) {
+            acc += w[f];
+            if ((int)c.size() < nt && acc * nt >= (int64_t)c.size() * tot && f + 1 < nFB) c.push_back(f + 1);
+        }
+        c.push_back(nFB);
+        return c;
+    }
+
+    // ---- the walks ---------------------------------------------------------
+    // The matrix terms of the rows [r0, r1), per source kind in source order:
+    // sum(fa, fb, twice, ReduceTerm) for the image Gram slices and the tile
+    // groups [c0, c1), prod(fa, fb, twice, PTerm) for the general points
+    // [g0, g1).  Only pairs fa >= fb that have a target (held) are visited;
+    // twice: the term also goes, transposed, to the twin target.
+    template <class Sum>
+    void matrix_images(int32_t r0, int32_t r1, Sum&& sum) const {
+        auto in = [&](int32_t f) { return f >= r0 && f < r1; };
+        for (const ImgSrc& s : isrc)
+            for (int g = 0; g < gseg; ++g) {
+                const int32_t idx = s.img * gseg + g;
+                if (s.cb >= 0 && in(s.cb)) sum(s.cb, s.cb, twice(s.cb, s.cb), ReduceTerm{kSrcU, idx, 0, 0, 1.f});
+                if (s.fq >= 0 && in(s.fq)) {
+                    if (s.cb >= 0) sum(s.fq, s.cb, twice(s.fq, s.cb), ReduceTerm{kSrcU, idx, 6, 0, 1.f});
+                    sum(s.fq, s.fq, twice(s.fq, s.fq), ReduceTerm{kSrcU, idx, 6, 6, 1.f});
+                }
+            }
+    }
+    template <class Sum>
+    void matrix_groups(int32_t c0, int32_t c1, int32_t r0, int32_t r1, Sum&& sum) const {
+        for (int32_t c = c0; c < c1; ++c) {
+            if (g_hi[c] < r0 || g_lo[c] >= r1) continue;
+            const ChunkDesc& cd = grp(c);
+            const int32_t* fs = &gfb[(size_t)c * kMaxSlots];
+            for (int a = 0; a < cd.n_slots; ++a) {
+                const int32_t fa = fs[a];
+                if (fa < r0 || fa >= r1) continue;
+                for (int b = 0; b < cd.n_slots; ++b) {
+                    const int32_t fb = fs[b];
+                    if (fa < fb || !held(fa, fb)) continue;
+                    sum(fa, fb, twice(fa, fb),
+                        ReduceTerm{kSrcTile, c, (int16_t)cd.slot_row[a], (int16_t)cd.slot_row[b], 1.f});
+                }
+            }
+        }
+    }
+    template <class Prod>
+    void matrix_points(int64_t g0, int64_t g1, int32_t r0, int32_t r1, Prod&& prod) const {
+        for (int64_t g = g0; g < g1; ++g) {
+            if (p_hi[g] < r0 || p_lo[g] >= r1) continue;
+            const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
+            const int64_t zb = pl.gz_off[g];
+            for (int32_t a = k0; a < k1; ++a) {   // columns ascend
+                const int32_t fa = pfb[a];
+                if (fa < r0) continue;
+                if (fa >= r1) break;
+                for (int32_t b = k0; b <= a; ++b)
+                    prod(fa, pfb[b], twice(fa, pfb[b]),
+                         PTerm{(int32_t)(zb + pl.gblk_z[a]), (int32_t)(zb + pl.gblk_z[b])});
+            }
+        }
+    }
+    template <class Sum, class Prod>
+    void walk_matrix(int32_t r0, int32_t r1, Sum&& sum, Prod&& prod) const {
+        matrix_images(r0, r1, sum);
+        matrix_groups(0, ngrp, r0, r1, sum);
+        matrix_points(0, pl.n_gpt, r0, r1, prod);
+    }
+    // The vector terms of the rows [r0, r1) in the order of their matrix
+    // terms' sources: img(f, row offset, slice) for an image slice (one rhs,
+    // one bF and one cnF term), tile(fa, ReduceTerm) for tile row 79 (-Z w) of
+    // a tile-group slot (rhs), pt(fa, PTerm) for a general point's w (rhs).
+    template <class Img>
+    void vector_images(int32_t r0, int32_t r1, Img&& img) const {
+        auto in = [&](int32_t f) { return f >= r0 && f < r1; };
+        for (const ImgSrc& s : isrc)
+            for (int g = 0; g < gseg; ++g) {
+                const int32_t idx = s.img * gseg + g;
+                if (s.cb >= 0 && in(s.cb)) img(s.cb, (int16_t)0, idx);
+                if (s.fq >= 0 && in(s.fq)) img(s.fq, (int16_t)6, idx);
+            }
+    }
+    template <class Tile>
+    void vector_groups(int32_t c0, int32_t c1, int32_t r0, int32_t r1, Tile&& tile) const {
+        for (int32_t c = c0; c < c1; ++c) {
+            if (g_hi[c] < r0 || g_lo[c] >= r1) continue;
+            const ChunkDesc& cd = grp(c);
+            for (int a = 0; a < cd.n_slots; ++a) {
+                const int32_t fa = gfb[(size_t)c * kMaxSlots + a];
+                if (fa >= r0 && fa < r1)
+                    tile(fa, ReduceTerm{kSrcTile, c, (int16_t)kTileWRow, (int16_t)cd.slot_row[a], 1.f});
+            }
+        }
+    }
+    template <class Pt>
+    void vector_points(int64_t g0, int64_t g1, int32_t r0, int32_t r1, Pt&& pt) const {
+        for (int64_t g = g0; g < g1; ++g) {
+            if (p_hi[g] < r0 || p_lo[g] >= r1) continue;
+            const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
+            const int64_t zb = pl.gz_off[g], wz = pl.gz_off[g + 1] - 3;
+            for (int32_t a = k0; a < k1; ++a) {
+                const int32_t fa = pfb[a];
+                if (fa < r0) continue;
+                if (fa >= r1) break;
+                pt(fa, PTerm{(int32_t)(zb + pl.gblk_z[a]), (int32_t)wz});
+            }
+        }
+    }
+    template <class Img, class Tile, class Pt>
+    void walk_vectors(int32_t r0, int32_t r1, Img&& img, Tile&& tile, Pt&& pt) const {
+        vector_images(r0, r1, img);
+        vector_groups(0, ngrp, r0, r1, tile);
+        vector_points(0, pl.n_gpt, r0, r1, pt);
+    }
+
+    // ---- stages --------------------------------------------------------------
+    void sources() {
+        if (band) {
+            pl.n_sband = (int64_t)ncam * Dp * 36;
+            pl.n_sarrow = (int64_t)nintr * ncam * 6 * pl.iw;
+            pl.n_scorner = (int64_t)nintr * nintr * pl.iw * pl.iw;
+        }
+        for (int img = 0; img < P.n_img; ++img) {
+            const int cb = pl.cam_blk[img], q = pl.intr_blk[P.img_intr[img]];
+            const bool seen = pl.img_obs_ptr[img + 1] != pl.img_obs_ptr[img];
+            if (!seen && cb < 0 && q < 0) continue;
+            // a landmark shard: an image none of this rank's observations sees
+            // contributes nothing here (its blocks come from the other ranks)
+            if (world > 1 && !seen) continue;
+            isrc.push_back({img, cb, q >= 0 ? ncam + q : -1});
+        }
+        g_lo.resize(ngrp); g_hi.resize(ngrp); p_lo.resize(pl.n_gpt); p_hi.resize(pl.n_gpt);
+        pfb.resize(pl.gblk_col.size());
+        gfb.resize((size_t)ngrp * kMaxSlots);
+        for (int32_t c = 0; c < ngrp; ++c) {
+            int32_t lo = INT32_MAX, hi = -1;
+            for (int a = 0; a < grp(c).n_slots; ++a) {
+                const int32_t f = fb_of_col(grp(c).slot_col[a]);
+                gfb[(size_t)c * kMaxSlots + a] = f;
+                lo = std::min(lo, f);
+                hi = std::max(hi, f);
+            }
+            g_lo[c] = lo;
+            g_hi[c] = hi;
+        }
+        parallel_ranges(pl.n_gpt, [&](int64_t g0, int64_t g1, int) {
+            for (int64_t g = g0; g < g1; ++g) {
+                const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
+                for (int32_t a = k0; a < k1; ++a) pfb[a] = fb_of_col(pl.gblk_col[a]);
+                p_lo[g] = k1 > k0 ? fb_of_col(pl.gblk_col[k0]) : INT32_MAX;   // columns ascend
+                p_hi[g] = k1 > k0 ? fb_of_col(pl.gblk_col[k1 - 1]) : -1;
+            }
+        });
+        tm.mark("terms_sources");
+    }
+
+    // per-row counts (the walks over all rows; the general points' matrix
+    // terms in closed form: planning time) and every row's first position
+    void row_counts() {
+        const size_t stride = (size_t)nFB + 1;
+        rc.assign((size_t)kNC * stride, 0);
+        matrix_images(0, nFB, [&](int32_t fa, int32_t, bool tw, const ReduceTerm&) { RC(kMc, fa) += tw ? 2 : 1; });
+        vector_images(0, nFB, [&](int32_t f, int16_t, int32_t) {
+            RC(kVc, f) += 1;
+            RC(kVb, f) += 1;
+        });
+        // tile groups and general points, per host range into private rows
+        std::vector<std::vector<int64_t>> part(16);
+        auto add_parts = [&] {
+            for (auto& p : part) {
+                for (size_t k = 0; k < p.size(); ++k) rc[k] += p[k];
+                p.clear();
+            }
+        };
+        parallel_ranges(ngrp, [&](int64_t c0, int64_t c1, int t) {
+            std::vector<int64_t>& r = part[t];
+            r.assign((size_t)kNC * stride, 0);
+            matrix_groups((int32_t)c0, (int32_t)c1, 0, nFB,
+                          [&](int32_t fa, int32_t, bool tw, const ReduceTerm&) { r[kMc * stride + fa] += tw ? 2 : 1; });
+            vector_groups((int32_t)c0, (int32_t)c1, 0, nFB,
+                          [&](int32_t fa, const ReduceTerm&) { r[kVc * stride + fa] += 1; });
+        });
+        add_parts();
+        parallel_ranges(pl.n_gpt, [&](int64_t g0, int64_t g1, int t) {
+            std::vector<int64_t>& r = part[t];
+            r.assign((size_t)kNC * stride, 0);
+            for (int64_t g = g0; g < g1; ++g) {
+                const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
+                int32_t first_i = k1;   // first intrinsics block (columns ascend)
+                for (int32_t a = k0; a < k1; ++a) {
+                    const int32_t fa = pfb[a];
+                    if (fa >= ncam && first_i == k1) first_i = a;
+                    r[kVp * stride + fa] += 1;
+                    const int64_t pairs = a - k0 + 1, dbl = band && fa >= ncam ? a - first_i : 0;
+                    r[kMp * stride + fa] += pairs + dbl;
+                }
+            }
+        });
+        add_parts();
+        // first position of every row in its list: matrix sum terms, then rhs,
+        // bF and cnF sum terms; matrix product terms, then rhs product terms
+        base.assign((size_t)kNC * stride + 1, 0);
+        for (int32_t f = 0; f < nFB; ++f) {
+            BS(kMc, f) = n_mc; n_mc += RC(kMc, f);
+            BS(kMp, f) = n_mp; n_mp += RC(kMp, f);
+            BS(kVc, f) = n_vc; n_vc += RC(kVc, f);
+            BS(kVp, f) = n_vp; n_vp += RC(kVp, f);
+            BS(kVb, f) = n_vb; n_vb += RC(kVb, f);
+        }
+        BS(kMc, nFB) = n_mc; BS(kMp, nFB) = n_mp;
+        n_terms = n_mc + n_vc + 2 * n_vb;
+        n_pterms = n_mp + n_vp;
+        SFM_REQUIRE(n_terms < INT32_MAX && n_pterms < INT32_MAX, SFM_ERR_UNSUPPORTED,
+                    "reduce plan of %lld sum / %lld product terms", (long long)n_terms, (long long)n_pterms);
+    }
+
+    // A grown plan (seed): the matrix rows before f0 -- the first F-block row
+    // a re-planned chunk or general point writes, or a new camera's -- are the
+    // seed's, targets and terms alike (the same sources in the same order), in
+    // place; only their image-slice offsets (behind the tiles in the source
+    // buffer, whose count changed) and dense destinations (the RCS grew) move.
+    void splice_seed() {
+        if (seed && seed->row_tgt.size() == (size_t)seed->nFB + 1 && seed->dense == pl.dense && seed->D == D &&
+            seed->gram_seg == pl.gram_seg && seed->iw == pl.iw && seed->nintr == nintr && world == 1) {
+            int32_t f = std::min(seed->ncam, ncam);
+            for (int32_t c = 0; c < ngrp; ++c)
+                if (pl.group_off[c] >= pl.reused_chunks) f = std::min(f, g_lo[c]);
+            for (int64_t g = pl.reused_gpts; g < pl.n_gpt; ++g) f = std::min(f, p_lo[g]);
+            if (f > 0 && f <= seed->nFB) {
+                t_keep = seed->row_tgt[f];
+                const bool tail = t_keep < (int64_t)seed->targets.size();
+                if (tail && seed->targets[t_keep].c_begin == BS(kMc, f) && seed->targets[t_keep].p_begin == BS(kMp, f) &&
+                    (int64_t)seed->terms.size() >= BS(kMc, f) && (int64_t)seed->pterms.size() >= BS(kMp, f))
+                    f0 = f;
+            }
+        }
+        if (f0 > 0) {
+            BAHostPlan& q = *seed;
+            pl.terms = std::move(q.terms);
+            pl.pterms = std::move(q.pterms);
+            pl.targets = std::move(q.targets);
+            pl.targets.resize(t_keep);
+            const SourceLayout ql(q.n_group(), q.n_img, q.iw);   // the seed's terms are resolved against this
+            const int64_t du = lay.o_u - ql.o_u, dub = lay.o_ub - ql.o_ub, ducn = lay.o_ucn - ql.o_ucn;
+            FlatTerm* T = pl.terms.data();
+            parallel_ranges(BS(kMc, f0), [&](int64_t a0, int64_t a1, int) {
+                for (int64_t k = a0; k < a1; ++k) {
+                    const int64_t o = T[k].off;
+                    T[k].off = o + (o >= ql.o_ucn ? ducn : o >= ql.o_ub ? dub : o >= ql.o_u ? du : 0);
+                }
+            });
+            if (!band)
+                for (ReduceTarget& t : pl.targets) {   // camera rows: (fa, fb) columns unchanged, the row stride grew
+                    const int64_t ca = t.dst / q.nF, cb = t.dst % q.nF;
+                    t.dst = ca * pl.nF + cb;
+                    t.ld = (int32_t)pl.nF;
+                }
+        } else {
+            pl.targets.clear();
+        }
+        grow_to(pl.terms, n_terms);
+        grow_to(pl.pterms, n_pterms);
+        tm.mark("terms_count");
+    }
+
+    // the matrix rows [cut[sg], cut[sg + 1]): targets and terms
+    void matrix_segment(int sg) {
+        const int32_t r0 = cut[sg], r1 = cut[sg + 1];
+        std::vector<int64_t> sbase(r1 - r0 + 1, 0);   // first slot of each row
+        for (int32_t f = r0; f < r1; ++f) sbase[f - r0 + 1] = sbase[f - r0] + row_slots(f);
+        const int64_t ns = sbase[r1 - r0];
+        // per slot: sum / product term counts, then write cursors
+        std::vector<int64_t> cs(ns, 0), ps(ns, 0);
+        auto S = [&](int32_t fa, int32_t fb) { return sbase[fa - r0] + slot_of(fa, fb); };
+        // (1) counts
+        walk_matrix(
+            r0, r1,
+            [&](int32_t fa, int32_t fb, bool tw, const ReduceTerm&) {
+                const int64_t q = S(fa, fb);
+                cs[q]++;
+                if (tw) cs[q - 1]++;
+            },
+            [&](int32_t fa, int32_t fb, bool tw, const PTerm&) {
+                const int64_t q = S(fa, fb);
+                ps[q]++;
+                if (tw) ps[q - 1]++;
+            });
+        // (2) targets in slot order; the counts become write cursors
+        auto& tg = seg_targets[sg];
+        seg_rows[sg].resize(r1 - r0);
+        int64_t c_at = BS(kMc, r0), p_at = BS(kMp, r0);
+        for (int32_t f = r0; f < r1; ++f)
+            for (int64_t s = (seg_rows[sg][f - r0] = (int32_t)tg.size(), 0); s < row_slots(f); ++s) {
+                const int64_t q = sbase[f - r0] + s;
+                const int64_t nc = cs[q], np = ps[q];
+                cs[q] = c_at;
+                ps[q] = p_at;
+                if (!band && nc == 0 && np == 0) continue;
+                ReduceTarget t = make_target(f, s);
+                t.c_begin = (int32_t)c_at; t.c_end = (int32_t)(c_at + nc);
+                t.p_begin = (int32_t)p_at; t.p_end = (int32_t)(p_at + np);
+                c_at += nc;
+                p_at += np;
+                tg.push_back(t);
+            }
+        // (3) the terms, sources in order
+        FlatTerm* T = pl.terms.data();
+        PTerm* PT = pl.pterms.data();
+        walk_matrix(
+            r0, r1,
+            [&](int32_t fa, int32_t fb, bool tw, ReduceTerm r) {
+                const int64_t q = S(fa, fb);
+                T[cs[q]++] = flat(r, false);
+                if (tw) {
+                    std::swap(r.roff, r.coff);
+                    T[cs[q - 1]++] = flat(r, false);
+                }
+            },
+            [&](int32_t fa, int32_t fb, bool tw, PTerm r) {
+                const int64_t q = S(fa, fb);
+                PT[ps[q]++] = r;
+                if (tw) {
+                    std::swap(r.za, r.zb);
+                    PT[ps[q - 1]++] = r;
+                }
+            });
+        // (4) every cursor stands at its target's end (an empty dense slot has
+        // no target: at its predecessor's end), and the last target ends where
+        // the per-row counts start the next row range
+        size_t ti = 0;
+        int64_t c_end = BS(kMc, r0), p_end = BS(kMp, r0);
+        bool ok = true;
+        for (int32_t f = r0; f < r1; ++f)
+            for (int64_t s = 0; s < row_slots(f); ++s) {
+                if (ti < tg.size() && (band || tg[ti].dst == dense_dst(f, (int32_t)s))) {
+                    c_end = tg[ti].c_end;
+                    p_end = tg[ti].p_end;
+                    ++ti;
+                }
+                const int64_t q = sbase[f - r0] + s;
+                ok = ok && cs[q] == c_end && ps[q] == p_end;
+            }
+        SFM_REQUIRE(ok && ti == tg.size() && c_end == BS(kMc, r1) && p_end == BS(kMp, r1), SFM_ERR_UNSUPPORTED,
+                    "reduce plan (internal): matrix rows [%d, %d): the terms written do not fill the targets counted",
+                    r0, r1);
+    }
+
+    // targets and terms of the matrix rows f0.., by row ranges
+    void matrix_rows() {
+        cut = row_cuts(f0, true);
+        const int nseg = (int)cut.size() - 1;
+        seg_targets.assign(nseg, {});
+        seg_rows.assign(nseg, {});
+        std::vector<int> seg_rc(nseg, SFM_OK);
+        parallel_segments(nseg, [&](int sg) {
+            seg_rc[sg] = guarded([&] {
+                matrix_segment(sg);
+                return SFM_OK;
+            });
+        });
+        for (int sg = 0; sg < nseg; ++sg)
+            if (seg_rc[sg] != SFM_OK) throw SfmError{seg_rc[sg]};
+        tm.mark("terms");
+    }
+
+    // the vector terms (rhs sum / product, bF, cnF) of the rows [r0, r1)
+    void vector_segment(int32_t r0, int32_t r1) {
+        FlatTerm* T = pl.terms.data();
+        PTerm* PT = pl.pterms.data();
+        // per row: the cursors of its rhs sum, rhs product, bF and cnF terms
+        std::vector<int64_t> vcur(4 * (size_t)(r1 - r0));
+        auto first = [&](int32_t f, int k) {
+            return k == 0 ? n_mc + BS(kVc, f) : k == 1 ? n_mp + BS(kVp, f) : n_mc + n_vc + (k - 2) * n_vb + BS(kVb, f);
+        };
+        for (int32_t f = r0; f < r1; ++f)
+            for (int k = 0; k < 4; ++k) vcur[4 * (f - r0) + k] = first(f, k);
+        walk_vectors(
+            r0, r1,
+            [&](int32_t f, int16_t ro, int32_t idx) {
+                int64_t* v = &vcur[4 * (f - r0)];
+                T[v[0]++] = flat(ReduceTerm{kSrcUb, idx, ro, 0, 1.f}, true);
+                T[v[2]++] = flat(ReduceTerm{kSrcUb, idx, ro, 0, 1.f}, true);
+                T[v[3]++] = flat(ReduceTerm{kSrcUcn, idx, ro, 0, 1.f}, true);
+            },
+            [&](int32_t fa, const ReduceTerm& r) { T[vcur[4 * (fa - r0)]++] = flat(r, true); },
+            [&](int32_t fa, const PTerm& r) { PT[vcur[4 * (fa - r0) + 1]++] = r; });
+        // every cursor stands at the end the per-row counts gave its list
+        bool ok = true;
+        for (int32_t f = r0; f < r1; ++f) {
+            const int64_t* v = &vcur[4 * (f - r0)];
+            ok = ok && v[0] == first(f, 0) + RC(kVc, f) && v[1] == first(f, 1) + RC(kVp, f) &&
+                 v[2] == first(f, 2) + RC(kVb, f) && v[3] == first(f, 3) + RC(kVb, f);
+        }
+        SFM_REQUIRE(ok, SFM_ERR_UNSUPPORTED,
+                    "reduce plan (internal): vector rows [%d, %d): the terms written do not fill the targets counted",
+                    r0, r1);
+    }
+
+    // every row's vector terms: the image slices, then tile row 79 (-Z w) in
+    // group order, then the general points' w, per row
+    void vector_rows() {
+        const std::vector<int32_t> vcut = row_cuts(0, false);
+        const int nv = (int)vcut.size() - 1;
+        std::vector<int> v_rc(nv, SFM_OK);
+        parallel_segments(nv, [&](int sg) {
+            v_rc[sg] = guarded([&] {
+                vector_segment(vcut[sg], vcut[sg + 1]);
+                return SFM_OK;
+            });
+        });
+        for (int sg = 0; sg < nv; ++sg)
+            if (v_rc[sg] != SFM_OK) throw SfmError{v_rc[sg]};
+        tm.mark("vector_terms");
+    }
+
+    void assemble_targets() {
+        {
+            // the matrix targets: the seed's rows before f0 (pl.targets already),
+            // then this plan's; every row's first target for the next grown plan
+            const int nseg = (int)cut.size() - 1;
+            size_t nt = pl.targets.size() + 3 * (size_t)nFB;
+            for (const auto& v : seg_targets) nt += v.size();
+            pl.targets.reserve(nt);
+            for (const auto& v : seg_targets) pl.targets.insert(pl.targets.end(), v.begin(), v.end());
+            pl.row_tgt.assign(nFB + 1, 0);
+            if (f0 > 0) std::copy(seed->row_tgt.begin(), seed->row_tgt.begin() + f0, pl.row_tgt.begin());
+            int64_t at = t_keep;
+            for (int sg = 0; sg < nseg; ++sg) {
+                for (int32_t f = cut[sg]; f < cut[sg + 1]; ++f) pl.row_tgt[f] = (int32_t)(at + seg_rows[sg][f - cut[sg]]);
+                at += (int64_t)seg_targets[sg].size();
+            }
+            pl.row_tgt[nFB] = (int32_t)at;
+        }
+        // vectors: rhs = bF - Z w, bF, cnF, per F block in order
+        for (int pass = 0; pass < 3; ++pass)
+            for (int32_t fb = 0; fb < nFB; ++fb) {
+                ReduceTarget t{};
+                t.dst = col_of_fb(fb);
+                t.dst_kind = pass == 0 ? kDstRhs : pass == 1 ? kDstBF : kDstCnF;
+                t.rows = size_of_fb(fb); t.cols = 1; t.ld = 1;
+                const int64_t c0 = pass == 0 ? n_mc + BS(kVc, fb) : n_mc + n_vc + (pass - 1) * n_vb + BS(kVb, fb);
+                const int64_t nc = pass == 0 ? RC(kVc, fb) : RC(kVb, fb);
+                t.c_begin = (int32_t)c0; t.c_end = (int32_t)(c0 + nc);
+                if (pass == 0) {
+                    t.p_begin = (int32_t)(n_mp + BS(kVp, fb));
+                    t.p_end = (int32_t)(t.p_begin + RC(kVp, fb));
+                } else {
+                    t.p_begin = t.p_end = (int32_t)n_pterms;
+                }
+                pl.targets.push_back(t);
+            }
+        pl.zero_targets.clear();
+        if (world > 1) {
+            // a shard gathers terms only into the blocks its points touch (about
+            // 1/world of the band); the others, which other shards write, go to a
+            // zero list that the reduce launch clears beside the real targets.
+            // (Dense plans list only this shard's blocks, so the solver clears
+            // their whole system before each reduce instead.)
+            size_t w = 0;
+            for (size_t t = 0; t < pl.targets.size(); ++t) {
+                const ReduceTarget& T = pl.targets[t];
+                if (T.c_begin != T.c_end || T.p_begin != T.p_end) pl.targets[w++] = T;
+                else pl.zero_targets.push_back(T);
+            }
+            pl.targets.resize(w);
+        }
+        tm.mark("targets");
+    }
+};
+
+void build_reduce_plan(const sfm_ba_problem& P, BAHostPlan& pl, PhaseTimer& tm, BAHostPlan* seed = nullptr) {
+    ReducePlanner rp(P, pl, tm, seed);
+    rp.sources();
+    rp.row_counts();
+    rp.splice_seed();
+    rp.matrix_rows();
+    rp.vector_rows();
+    rp.assemble_targets();
+}
 
 }  // namespace
 
@@ -1270,562 +1917,6 @@ bool build_plan_grown(const sfm_ba_problem& P, const GrowPrev& prev, BAHostPlan&
     return true;
 }
 
-namespace {
-
-void build_reduce_plan(const sfm_ba_problem& P, BAHostPlan& pl, PhaseTimer& tm, BAHostPlan* seed) {
-    const int world = pl.world;
-    // ---- reduce plan -----------------------------------------------------------
-    // Every matrix block (a, b), a >= b in F-block order (cameras, then
-    // intrinsics), is a target summing its terms in a fixed order: sum terms
-    // (image Gram slices in image order, then chunk tile sub-blocks in tile
-    // group order) and product terms (general points in order); vectors (rhs,
-    // bF, cnF) likewise per block -- so every sum is bit-reproducible.  Both
-    // lists are laid out target after target.  They are built by a counting
-    // scatter over F-block rows, without materialising or sorting (key, term)
-    // lists: per-row term counts first (one pass over the sources, O(blocks)),
-    // which fix every row's first position; then each host thread takes a
-    // range of rows, counts its targets' terms, and writes every term of its
-    // rows straight to its final place, visiting the sources in their order.
-    const int32_t nFB = pl.nFB, ncam = pl.ncam, nintr = pl.nintr, D = pl.D;
-    const int Dp = D + 1;
-    const bool band = !pl.dense;
-    if (band) {
-        pl.n_sband = (int64_t)ncam * Dp * 36;
-        pl.n_sarrow = (int64_t)nintr * ncam * 6 * pl.iw;
-        pl.n_scorner = (int64_t)nintr * nintr * pl.iw * pl.iw;
-    }
-    auto fb_of_col = [&](int64_t col) -> int32_t {
-        return col < pl.nb ? (int32_t)(col / 6) : (int32_t)(ncam + (col - pl.nb) / pl.iw);
-    };
-    auto col_of_fb = [&](int32_t b) -> int64_t { return b < ncam ? 6LL * b : pl.nb + (int64_t)pl.iw * (b - ncam); };
-    auto size_of_fb = [&](int32_t b) { return b < ncam ? 6 : pl.iw; };
-    // Terms are stored resolved against the solver's one source buffer
-    // [chunk tiles | U | Ub | Ucn] (ba_solver.cpp create_plan: the same layout)
-    const int64_t fw = 6 + pl.iw;
-    const int64_t o_u = std::max<int64_t>(pl.n_group(), 1) * kTileR * kTileR, o_ub = o_u + fw * fw * P.n_img * kGramSeg,
-                  o_ucn = o_ub + fw * P.n_img * kGramSeg;
-    auto flat = [&](const ReduceTerm& q, bool vec) {
-        FlatTerm f{};
-        f.sign = q.sign;
-        f.mode = kFlatRows;
-        switch (q.kind) {
-            case kSrcTile: {
-                // slot blocks occupy disjoint tile rows, so a block of two
-                // slots is wholly below or wholly above the diagonal
-                const int64_t base = (int64_t)q.index * kTileR * kTileR;
-                if (vec || q.roff > q.coff) {
-                    f.off = base + q.roff * kTileR + q.coff;
-                    f.rs = vec ? 1 : kTileR;
-                } else if (q.roff < q.coff) {
-                    f.off = base + q.coff * kTileR + q.roff;
-                    f.rs = 1;
-                    f.mode = kFlatTrans;
-                } else {   // rs = the origin's offset within the tile
-                    f.off = base + q.roff * kTileR + q.coff;
-                    f.rs = (int16_t)(q.roff * kTileR + q.coff);
-                    f.mode = kFlatSym;
-                }
-                break;
-            }
-            case kSrcU:
-                f.off = o_u + q.index * fw * fw + q.roff * fw + q.coff;
-                f.rs = (int16_t)fw;
-                break;
-            case kSrcUb:
-                f.off = o_ub + q.index * fw + q.roff;
-                f.rs = 1;
-                break;
-            default:
-                f.off = o_ucn + q.index * fw + q.roff;
-                f.rs = 1;
-                break;
-        }
-        return f;
-    };
-    // band: a corner block (k, l), k < l, is stored too, as the transpose of
-    // (l, k): terms of an off-diagonal corner key go to two targets
-    auto twice = [&](int32_t fa, int32_t fb) { return band && fb >= ncam && fb != fa; };
-    // a tile group's window can be wider than the band: its slot pairs
-    // further apart than D are structurally zero (no point sees both) and
-    // have no target
-    auto held = [&](int32_t fa, int32_t fb) { return !band || fa >= ncam || fa - fb <= D; };
-    // the images that contribute Gram slices: (image, camera block, F block of its intrinsics)
-    struct ImgSrc {
-        int32_t img, cb, fq;
-    };
-    std::vector<ImgSrc> isrc;
-    for (int img = 0; img < P.n_img; ++img) {
-        const int cb = pl.cam_blk[img], q = pl.intr_blk[P.img_intr[img]];
-        const bool seen = pl.img_obs_ptr[img + 1] != pl.img_obs_ptr[img];
-        if (!seen && cb < 0 && q < 0) continue;
-        // a landmark shard: an image none of this rank's observations sees
-        // contributes nothing here (its blocks come from the other ranks)
-        if (world > 1 && !seen) continue;
-        isrc.push_back({img, cb, q >= 0 ? ncam + q : -1});
-    }
-    const int32_t ngrp = (int32_t)pl.n_group();
-    auto grp = [&](int32_t c) -> const ChunkDesc& { return pl.chunks[pl.group_off[c]]; };
-    // F-block range of every tile group and general point (rows they write)
-    std::vector<int32_t> g_lo(ngrp), g_hi(ngrp), p_lo(pl.n_gpt), p_hi(pl.n_gpt);
-    // F block of every general-point block (pfb) and tile-group slot (gfb)
-    std::vector<int32_t> pfb(pl.gblk_col.size()), gfb((size_t)ngrp * kMaxSlots);
-    for (int32_t c = 0; c < ngrp; ++c) {
-        int32_t lo = INT32_MAX, hi = -1;
-        for (int a = 0; a < grp(c).n_slots; ++a) {
-            const int32_t f = fb_of_col(grp(c).slot_col[a]);
-            gfb[(size_t)c * kMaxSlots + a] = f;
-            lo = std::min(lo, f);
-            hi = std::max(hi, f);
-        }
-        g_lo[c] = lo;
-        g_hi[c] = hi;
-    }
-    parallel_ranges(pl.n_gpt, [&](int64_t g0, int64_t g1, int) {
-        for (int64_t g = g0; g < g1; ++g) {
-            const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
-            for (int32_t a = k0; a < k1; ++a) pfb[a] = fb_of_col(pl.gblk_col[a]);
-            p_lo[g] = k1 > k0 ? fb_of_col(pl.gblk_col[k0]) : INT32_MAX;   // columns ascend
-            p_hi[g] = k1 > k0 ? fb_of_col(pl.gblk_col[k1 - 1]) : -1;
-        }
-    });
-    tm.mark("terms_sources");
-
-    // ---- per-row counts: matrix sum / product terms, rhs sum / product
-    // terms, image slices (bF and cnF) ------------------------------------------
-    enum { kMc, kMp, kVc, kVp, kVb, kNC };
-    std::vector<int64_t> rc((size_t)kNC * (nFB + 1), 0);
-    auto RC = [&](int w, int32_t f) -> int64_t& { return rc[(size_t)w * (nFB + 1) + f]; };
-    const int32_t gseg = pl.gram_seg;
-    for (const ImgSrc& s : isrc) {
-        if (s.cb >= 0) {
-            RC(kMc, s.cb) += gseg;
-            if (s.fq >= 0) RC(kMc, s.fq) += gseg;
-            RC(kVc, s.cb) += gseg;
-            RC(kVb, s.cb) += gseg;
-        }
-        if (s.fq >= 0) {
-            RC(kMc, s.fq) += gseg;
-            RC(kVc, s.fq) += gseg;
-            RC(kVb, s.fq) += gseg;
-        }
-    }
-    {
-        // tile groups and general points, per host range into private rows
-        std::vector<std::vector<int64_t>> part(16);
-        auto acc_groups = [&](int64_t c0, int64_t c1, std::vector<int64_t>& r) {
-            for (int64_t c = c0; c < c1; ++c) {
-                const ChunkDesc& cd = grp((int32_t)c);
-                for (int a = 0; a < cd.n_slots; ++a) {
-                    const int32_t fa = gfb[(size_t)c * kMaxSlots + a];
-                    r[(size_t)kVc * (nFB + 1) + fa] += 1;
-                    for (int b = 0; b < cd.n_slots; ++b) {
-                        const int32_t fb = gfb[(size_t)c * kMaxSlots + b];
-                        if (fa >= fb && held(fa, fb)) r[(size_t)kMc * (nFB + 1) + fa] += twice(fa, fb) ? 2 : 1;
-                    }
-                }
-            }
-        };
-        auto acc_points = [&](int64_t g0, int64_t g1, std::vector<int64_t>& r) {
-            for (int64_t g = g0; g < g1; ++g) {
-                const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
-                int32_t first_i = k1;   // first intrinsics block (columns ascend)
-                for (int32_t a = k0; a < k1; ++a) {
-                    const int32_t fa = pfb[a];
-                    if (fa >= ncam && first_i == k1) first_i = a;
-                    r[(size_t)kVp * (nFB + 1) + fa] += 1;
-                    const int64_t pairs = a - k0 + 1, dbl = band && fa >= ncam ? a - first_i : 0;
-                    r[(size_t)kMp * (nFB + 1) + fa] += pairs + dbl;
-                }
-            }
-        };
-        parallel_ranges(ngrp, [&](int64_t c0, int64_t c1, int t) {
-            part[t].assign((size_t)kNC * (nFB + 1), 0);
-            acc_groups(c0, c1, part[t]);
-        });
-        for (auto& p : part) {
-            if (p.empty()) continue;
-            for (size_t k = 0; k < p.size(); ++k) rc[k] += p[k];
-            p.clear();
-        }
-        parallel_ranges(pl.n_gpt, [&](int64_t g0, int64_t g1, int t) {
-            part[t].assign((size_t)kNC * (nFB + 1), 0);
-            acc_points(g0, g1, part[t]);
-        });
-        for (auto& p : part)
-            for (size_t k = 0; k < p.size(); ++k) rc[k] += p[k];
-    }
-    // first position of every row in its list: matrix sum terms, then rhs,
-    // bF and cnF sum terms; matrix product terms, then rhs product terms
-    std::vector<int64_t> base((size_t)kNC * (nFB + 1) + 1, 0);
-    auto BS = [&](int w, int32_t f) -> int64_t& { return base[(size_t)w * (nFB + 1) + f]; };
-    int64_t n_mc = 0, n_mp = 0, n_vc = 0, n_vp = 0, n_vb = 0;
-    for (int32_t f = 0; f < nFB; ++f) {
-        BS(kMc, f) = n_mc; n_mc += RC(kMc, f);
-        BS(kMp, f) = n_mp; n_mp += RC(kMp, f);
-        BS(kVc, f) = n_vc; n_vc += RC(kVc, f);
-        BS(kVp, f) = n_vp; n_vp += RC(kVp, f);
-        BS(kVb, f) = n_vb; n_vb += RC(kVb, f);
-    }
-    BS(kMc, nFB) = n_mc; BS(kMp, nFB) = n_mp;
-    const int64_t n_terms = n_mc + n_vc + 2 * n_vb, n_pterms = n_mp + n_vp;
-    SFM_REQUIRE(n_terms < INT32_MAX && n_pterms < INT32_MAX, SFM_ERR_UNSUPPORTED,
-                "reduce plan of %lld sum / %lld product terms", (long long)n_terms, (long long)n_pterms);
-    // A grown plan (seed): the matrix rows before f0 -- the first F-block row
-    // a re-planned chunk or general point writes, or a new camera's -- are the
-    // seed's, targets and terms alike (the same sources in the same order), in
-    // place; only their image-slice offsets (behind the tiles in the source
-    // buffer, whose count changed) and dense destinations (the RCS grew) move.
-    int32_t f0 = 0;
-    int64_t t_keep = 0;   // the seed's targets kept
-    if (seed && seed->row_tgt.size() == (size_t)seed->nFB + 1 && seed->dense == pl.dense && seed->D == D &&
-        seed->gram_seg == pl.gram_seg && seed->iw == pl.iw && seed->nintr == nintr && world == 1) {
-        int32_t f = std::min(seed->ncam, ncam);
-        for (int32_t c = 0; c < ngrp; ++c)
-            if (pl.group_off[c] >= pl.reused_chunks) f = std::min(f, g_lo[c]);
-        for (int64_t g = pl.reused_gpts; g < pl.n_gpt; ++g) f = std::min(f, p_lo[g]);
-        if (f > 0 && f <= seed->nFB) {
-            t_keep = seed->row_tgt[f];
-            const bool tail = t_keep < (int64_t)seed->targets.size();
-            if (tail && seed->targets[t_keep].c_begin == BS(kMc, f) && seed->targets[t_keep].p_begin == BS(kMp, f) &&
-                (int64_t)seed->terms.size() >= BS(kMc, f) && (int64_t)seed->pterms.size() >= BS(kMp, f))
-                f0 = f;
-        }
-    }
-    if (f0 > 0) {
-        BAHostPlan& q = *seed;
-        pl.terms = std::move(q.terms);
-        pl.pterms = std::move(q.pterms);
-        pl.targets = std::move(q.targets);
-        pl.targets.resize(t_keep);
-        const int64_t q_u = std::max<int64_t>(q.n_group(), 1) * kTileR * kTileR,
-                      q_ub = q_u + fw * fw * q.n_img * kGramSeg, q_ucn = q_ub + fw * q.n_img * kGramSeg;
-        const int64_t du = o_u - q_u, dub = o_ub - q_ub, ducn = o_ucn - q_ucn;
-        FlatTerm* T = pl.terms.data();
-        parallel_ranges(BS(kMc, f0), [&](int64_t a0, int64_t a1, int) {
-            for (int64_t k = a0; k < a1; ++k) {
-                const int64_t o = T[k].off;
-                T[k].off = o + (o >= q_ucn ? ducn : o >= q_ub ? dub : o >= q_u ? du : 0);
-            }
-        });
-        if (!band)
-            for (ReduceTarget& t : pl.targets) {   // camera rows: (fa, fb) columns unchanged, the row stride grew
-                const int64_t ca = t.dst / q.nF, cb = t.dst % q.nF;
-                t.dst = ca * pl.nF + cb;
-                t.ld = (int32_t)pl.nF;
-            }
-    } else {
-        pl.targets.clear();
-    }
-    grow_to(pl.terms, n_terms);
-    grow_to(pl.pterms, n_pterms);
-    tm.mark("terms_count");
-
-    // ---- targets and terms, by row ranges ----------------------------------
-    // matrix targets of row fa: band -- the band blocks (fa, fa-d), d from
-    // min(D, fa) down to 0; an intrinsics row ncam+m: the arrow (m, i) for
-    // every camera, then per corner column l <= m the transposed (l, m) (l <
-    // m) and (m, l) -- the order a stable sort of the targets by key gives.
-    // Dense: every block (fa, fb <= fa) that receives a term.
-    auto row_slots = [&](int32_t f) -> int64_t {
-        if (!band) return (int64_t)f + 1;
-        return f < ncam ? std::min(D, f) + 1 : ncam + 2 * (f - ncam) + 1;
-    };
-    // slot of (fa, fb) within row fa; *second: a transposed twin at slot - 1
-    auto slot_of = [&](int32_t fa, int32_t fb) -> int64_t {
-        if (!band) return fb;
-        if (fa < ncam) return fb - (fa - std::min(D, fa));
-        if (fb < ncam) return fb;
-        return ncam + 2 * (fb - ncam) + (fb != fa ? 1 : 0);   // the (fa, fb) target; its twin precedes it
-    };
-    auto make_target = [&](int32_t fa, int64_t s) {
-        ReduceTarget t{};
-        if (!band) {
-            const int32_t fb = (int32_t)s;
-            t.dst = col_of_fb(fa) * pl.nF + col_of_fb(fb);
-            t.dst_kind = kDstDense;
-            t.rows = size_of_fb(fa); t.cols = size_of_fb(fb); t.ld = (int32_t)pl.nF;
-        } else if (fa < ncam) {
-            const int d = std::min(D, fa) - (int)s;
-            t.dst = ((int64_t)fa * Dp + d) * 36;
-            t.dst_kind = kDstBand;
-            t.rows = 6; t.cols = 6; t.ld = 6;
-        } else if (s < ncam) {
-            t.dst = ((int64_t)(fa - ncam) * ncam + s) * 6 * pl.iw;
-            t.dst_kind = kDstArrow;
-            t.rows = pl.iw; t.cols = 6; t.ld = 6;
-        } else {
-            const int m = fa - ncam, u = (int)(s - ncam), lp = u / 2;
-            const bool trans = (u & 1) == 0 && lp < m;
-            const int k = trans ? lp : m, l = trans ? m : lp;
-            t.dst = ((int64_t)k * nintr + l) * pl.iw * pl.iw;
-            t.dst_kind = kDstCorner;
-            t.rows = pl.iw; t.cols = pl.iw; t.ld = pl.iw;
-        }
-        return t;
-    };
-    // row ranges of about equal work (terms, plus the row's targets)
-    // (matrix rows f0.. here; every row's vector terms below)
-    auto row_cuts = [&](int32_t fa0, bool matrix) {
-        std::vector<int32_t> cut{fa0};
-        int64_t tot = 0;
-        std::vector<int64_t> w(nFB);
-        for (int32_t f = fa0; f < nFB; ++f) {
-            w[f] = matrix ? RC(kMc, f) + RC(kMp, f) + row_slots(f) : RC(kVc, f) + RC(kVp, f) + 2 * RC(kVb, f);
-            tot += w[f];
-        }
-        const int nt = tot < 65536 ? 1 : std::min<int>(PlanPool::width(), std::max(1, nFB - fa0));
-        int64_t acc = 0;
-        for (int32_t f = fa0; f < nFB; ++f) {
-            acc += w[f];
-            if ((int)cut.size() < nt && acc * nt >= (int64_t)cut.size() * tot && f + 1 < nFB) cut.push_back(f + 1);
-        }
-        cut.push_back(nFB);
-        return cut;
-    };
-    const std::vector<int32_t> cut = row_cuts(f0, true);
-    const int nseg = (int)cut.size() - 1;
-    std::vector<std::vector<ReduceTarget>> seg_targets(nseg);
-    std::vector<std::vector<int32_t>> seg_rows(nseg);   // each row's first target within its segment
-    std::vector<int> seg_rc(nseg, SFM_OK);
-    parallel_segments(nseg, [&](int sg) {
-        seg_rc[sg] = guarded([&] {
-            const int32_t r0 = cut[sg], r1 = cut[sg + 1];
-            std::vector<int64_t> sbase(r1 - r0 + 1, 0);   // first slot of each row
-            for (int32_t f = r0; f < r1; ++f) sbase[f - r0 + 1] = sbase[f - r0] + row_slots(f);
-            const int64_t ns = sbase[r1 - r0];
-            // per slot: sum / product term counts, then write cursors
-            std::vector<int64_t> cs(ns, 0), ps(ns, 0);
-            auto S = [&](int32_t fa, int32_t fb) { return sbase[fa - r0] + slot_of(fa, fb); };
-            auto in = [&](int32_t f) { return f >= r0 && f < r1; };
-            // (1) counts
-            for (const ImgSrc& s : isrc) {
-                if (s.cb >= 0 && in(s.cb)) cs[S(s.cb, s.cb)] += gseg;
-                if (s.fq >= 0 && in(s.fq)) {
-                    if (s.cb >= 0) cs[S(s.fq, s.cb)] += gseg;
-                    cs[S(s.fq, s.fq)] += gseg;
-                }
-            }
-            for (int32_t c = 0; c < ngrp; ++c) {
-                if (g_hi[c] < r0 || g_lo[c] >= r1) continue;
-                const ChunkDesc& cd = grp(c);
-                for (int a = 0; a < cd.n_slots; ++a) {
-                    const int32_t fa = gfb[(size_t)c * kMaxSlots + a];
-                    if (!in(fa)) continue;
-                    for (int b = 0; b < cd.n_slots; ++b) {
-                        const int32_t fb = gfb[(size_t)c * kMaxSlots + b];
-                        if (fa < fb || !held(fa, fb)) continue;
-                        const int64_t q = S(fa, fb);
-                        cs[q]++;
-                        if (twice(fa, fb)) cs[q - 1]++;
-                    }
-                }
-            }
-            for (int64_t g = 0; g < pl.n_gpt; ++g) {
-                if (p_hi[g] < r0 || p_lo[g] >= r1) continue;
-                const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
-                for (int32_t a = k0; a < k1; ++a) {
-                    const int32_t fa = pfb[a];
-                    if (fa < r0) continue;
-                    if (fa >= r1) break;
-                    for (int32_t b = k0; b <= a; ++b) {
-                        const int32_t fb = pfb[b];
-                        const int64_t q = S(fa, fb);
-                        ps[q]++;
-                        if (twice(fa, fb)) ps[q - 1]++;
-                    }
-                }
-            }
-            // (2) targets in slot order; the counts become write cursors
-            auto& tg = seg_targets[sg];
-            seg_rows[sg].resize(r1 - r0);
-            int64_t c_at = BS(kMc, r0), p_at = BS(kMp, r0);
-            for (int32_t f = r0; f < r1; ++f)
-                for (int64_t s = (seg_rows[sg][f - r0] = (int32_t)tg.size(), 0); s < row_slots(f); ++s) {
-                    const int64_t q = sbase[f - r0] + s;
-                    const int64_t nc = cs[q], np = ps[q];
-                    cs[q] = c_at;
-                    ps[q] = p_at;
-                    if (!band && nc == 0 && np == 0) continue;
-                    ReduceTarget t = make_target(f, s);
-                    t.c_begin = (int32_t)c_at; t.c_end = (int32_t)(c_at + nc);
-                    t.p_begin = (int32_t)p_at; t.p_end = (int32_t)(p_at + np);
-                    c_at += nc;
-                    p_at += np;
-                    tg.push_back(t);
-                }
-            // (3) the terms, sources in order
-            FlatTerm* T = pl.terms.data();
-            PTerm* PT = pl.pterms.data();
-            auto put = [&](int64_t q, bool tw, ReduceTerm r) {
-                T[cs[q]++] = flat(r, false);
-                if (tw) {
-                    std::swap(r.roff, r.coff);
-                    T[cs[q - 1]++] = flat(r, false);
-                }
-            };
-            auto put_p = [&](int64_t q, bool tw, PTerm r) {
-                PT[ps[q]++] = r;
-                if (tw) {
-                    std::swap(r.za, r.zb);
-                    PT[ps[q - 1]++] = r;
-                }
-            };
-            for (const ImgSrc& s : isrc)
-                for (int g = 0; g < gseg; ++g) {
-                    const int32_t idx = s.img * gseg + g;
-                    if (s.cb >= 0 && in(s.cb)) put(S(s.cb, s.cb), false, ReduceTerm{kSrcU, idx, 0, 0, 1.f});
-                    if (s.fq >= 0 && in(s.fq)) {
-                        if (s.cb >= 0) put(S(s.fq, s.cb), false, ReduceTerm{kSrcU, idx, 6, 0, 1.f});
-                        put(S(s.fq, s.fq), false, ReduceTerm{kSrcU, idx, 6, 6, 1.f});
-                    }
-                }
-            for (int32_t c = 0; c < ngrp; ++c) {
-                if (g_hi[c] < r0 || g_lo[c] >= r1) continue;
-                const ChunkDesc& cd = grp(c);
-                for (int a = 0; a < cd.n_slots; ++a) {
-                    const int32_t fa = gfb[(size_t)c * kMaxSlots + a];
-                    if (!in(fa)) continue;
-                    for (int b = 0; b < cd.n_slots; ++b) {
-                        const int32_t fb = gfb[(size_t)c * kMaxSlots + b];
-                        if (fa < fb || !held(fa, fb)) continue;
-                        put(S(fa, fb), twice(fa, fb),
-                            ReduceTerm{kSrcTile, c, (int16_t)cd.slot_row[a], (int16_t)cd.slot_row[b], 1.f});
-                    }
-                }
-            }
-            for (int64_t g = 0; g < pl.n_gpt; ++g) {
-                if (p_hi[g] < r0 || p_lo[g] >= r1) continue;
-                const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
-                const int64_t zb = pl.gz_off[g];
-                for (int32_t a = k0; a < k1; ++a) {
-                    const int32_t fa = pfb[a];
-                    if (fa < r0) continue;
-                    if (fa >= r1) break;
-                    for (int32_t b = k0; b <= a; ++b) {
-                        const int32_t fb = pfb[b];
-                        put_p(S(fa, fb), twice(fa, fb), PTerm{(int32_t)(zb + pl.gblk_z[a]), (int32_t)(zb + pl.gblk_z[b])});
-                    }
-                }
-            }
-            return SFM_OK;
-        });
-    });
-    for (int sg = 0; sg < nseg; ++sg)
-        if (seg_rc[sg] != SFM_OK) throw SfmError{seg_rc[sg]};
-    tm.mark("terms");
-    // ---- every row's vector terms (rhs sum / product, bF, cnF): the image
-    // slices, then tile row 79 (-Z w) in group order, then the general points'
-    // w, per row -- the order of its matrix terms' sources -----------------------
-    {
-        const std::vector<int32_t> vcut = row_cuts(0, false);
-        const int nv = (int)vcut.size() - 1;
-        std::vector<int> v_rc(nv, SFM_OK);
-        parallel_segments(nv, [&](int sg) {
-            v_rc[sg] = guarded([&] {
-                const int32_t r0 = vcut[sg], r1 = vcut[sg + 1];
-                auto in = [&](int32_t f) { return f >= r0 && f < r1; };
-                FlatTerm* T = pl.terms.data();
-                PTerm* PT = pl.pterms.data();
-                std::vector<int64_t> vcur(4 * (size_t)(r1 - r0));
-                for (int32_t f = r0; f < r1; ++f) {
-                    vcur[4 * (f - r0) + 0] = n_mc + BS(kVc, f);
-                    vcur[4 * (f - r0) + 1] = n_mp + BS(kVp, f);
-                    vcur[4 * (f - r0) + 2] = n_mc + n_vc + BS(kVb, f);
-                    vcur[4 * (f - r0) + 3] = n_mc + n_vc + n_vb + BS(kVb, f);
-                }
-                auto put_v = [&](int32_t f, int16_t ro, int32_t idx) {
-                    int64_t* v = &vcur[4 * (f - r0)];
-                    T[v[0]++] = flat(ReduceTerm{kSrcUb, idx, ro, 0, 1.f}, true);
-                    T[v[2]++] = flat(ReduceTerm{kSrcUb, idx, ro, 0, 1.f}, true);
-                    T[v[3]++] = flat(ReduceTerm{kSrcUcn, idx, ro, 0, 1.f}, true);
-                };
-                for (const ImgSrc& s : isrc)
-                    for (int g = 0; g < gseg; ++g) {
-                        const int32_t idx = s.img * gseg + g;
-                        if (s.cb >= 0 && in(s.cb)) put_v(s.cb, 0, idx);
-                        if (s.fq >= 0 && in(s.fq)) put_v(s.fq, 6, idx);
-                    }
-                for (int32_t c = 0; c < ngrp; ++c) {
-                    if (g_hi[c] < r0 || g_lo[c] >= r1) continue;
-                    const ChunkDesc& cd = grp(c);
-                    for (int a = 0; a < cd.n_slots; ++a) {
-                        const int32_t fa = gfb[(size_t)c * kMaxSlots + a];
-                        if (in(fa))   // rhs contribution (-Z w) from tile row 79
-                            T[vcur[4 * (fa - r0)]++] =
-                                flat(ReduceTerm{kSrcTile, c, (int16_t)kTileWRow, (int16_t)cd.slot_row[a], 1.f}, true);
-                    }
-                }
-                for (int64_t g = 0; g < pl.n_gpt; ++g) {
-                    if (p_hi[g] < r0 || p_lo[g] >= r1) continue;
-                    const int32_t k0 = pl.gblk_off[g], k1 = pl.gblk_off[g + 1];
-                    const int64_t zb = pl.gz_off[g], wz = pl.gz_off[g + 1] - 3;
-                    for (int32_t a = k0; a < k1; ++a) {
-                        const int32_t fa = pfb[a];
-                        if (fa < r0) continue;
-                        if (fa >= r1) break;
-                        PT[vcur[4 * (fa - r0) + 1]++] = PTerm{(int32_t)(zb + pl.gblk_z[a]), (int32_t)wz};
-                    }
-                }
-                return SFM_OK;
-            });
-        });
-        for (int sg = 0; sg < nv; ++sg)
-            if (v_rc[sg] != SFM_OK) throw SfmError{v_rc[sg]};
-    }
-    tm.mark("vector_terms");
-    {
-        // the matrix targets: the seed's rows before f0 (pl.targets already),
-        // then this plan's; every row's first target for the next grown plan
-        size_t nt = pl.targets.size() + 3 * (size_t)nFB;
-        for (const auto& v : seg_targets) nt += v.size();
-        pl.targets.reserve(nt);
-        for (const auto& v : seg_targets) pl.targets.insert(pl.targets.end(), v.begin(), v.end());
-        pl.row_tgt.assign(nFB + 1, 0);
-        if (f0 > 0) std::copy(seed->row_tgt.begin(), seed->row_tgt.begin() + f0, pl.row_tgt.begin());
-        int64_t at = t_keep;
-        for (int sg = 0; sg < nseg; ++sg) {
-            for (int32_t f = cut[sg]; f < cut[sg + 1]; ++f) pl.row_tgt[f] = (int32_t)(at + seg_rows[sg][f - cut[sg]]);
-            at += (int64_t)seg_targets[sg].size();
-        }
-        pl.row_tgt[nFB] = (int32_t)at;
-    }
-    // vectors: rhs = bF - Z w, bF, cnF, per F block in order
-    for (int pass = 0; pass < 3; ++pass)
-        for (int32_t fb = 0; fb < nFB; ++fb) {
-            ReduceTarget t{};
-            t.dst = col_of_fb(fb);
-            t.dst_kind = pass == 0 ? kDstRhs : pass == 1 ? kDstBF : kDstCnF;
-            t.rows = size_of_fb(fb); t.cols = 1; t.ld = 1;
-            const int64_t c0 = pass == 0 ? n_mc + BS(kVc, fb) : n_mc + n_vc + (pass - 1) * n_vb + BS(kVb, fb);
-            const int64_t nc = pass == 0 ? RC(kVc, fb) : RC(kVb, fb);
-            t.c_begin = (int32_t)c0; t.c_end = (int32_t)(c0 + nc);
-            if (pass == 0) {
-                t.p_begin = (int32_t)(n_mp + BS(kVp, fb));
-                t.p_end = (int32_t)(t.p_begin + RC(kVp, fb));
-            } else {
-                t.p_begin = t.p_end = (int32_t)n_pterms;
-            }
-            pl.targets.push_back(t);
-        }
-    pl.zero_targets.clear();
-    if (world > 1) {
-        // a shard gathers terms only into the blocks its points touch (about
-        // 1/world of the band); the others, which other shards write, go to a
-        // zero list that the reduce launch clears beside the real targets.
-        // (Dense plans list only this shard's blocks, so the solver clears
-        // their whole system before each reduce instead.)
-        size_t w = 0;
-        for (size_t t = 0; t < pl.targets.size(); ++t) {
-            const ReduceTarget& T = pl.targets[t];
-            if (T.c_begin != T.c_end || T.p_begin != T.p_end) pl.targets[w++] = T;
-            else pl.zero_targets.push_back(T);
-        }
-        pl.targets.resize(w);
-    }
-    tm.mark("targets");
-}
-
-}  // namespace
 
 }  // namespace sfm
 

@@ -135,17 +135,16 @@ bool cache_enabled_for_growth() {
     return on;
 }
 
-// The plan of a problem: from scratch, or -- seed set (sfm_ba_solve's plan
-// cache, a problem grown from the previous call's, GrowPrev) -- grown from
-// the seed plan (build_plan_grown: the same arrays; the measurements are
-// gathered into shard order on the device).  Returns false, with nothing
-// done and the seed intact, when the seed cannot seed this problem.
-bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr, const double* intr,
-                 const double* X, sfm_ba_plan* seed = nullptr, const GrowPrev* prev = nullptr) {
+// ---- create_plan's stages, in their order (which is the order of the HIP
+// calls on the context's stream) ------------------------------------------------
+
+// The host plan: fresh, or grown from the seed's (false: the seed cannot seed
+// this problem; nothing done).  The shard's observation arrays are uploaded
+// as soon as the planner has them, beside the rest of the planning.
+bool plan_host(sfm_ba_plan* pl, const sfm_ba_problem& prob, sfm_ba_plan* seed, const GrowPrev* prev, PhaseTimer& tm) {
     sfm_ctx* ctx = pl->ctx;
     hipStream_t s = ctx->stream;
     BAHostPlan& h = pl->hp;
-    PhaseTimer tm("create_plan");
     h.on_shard_ready = [&](BAHostPlan& hp) {
         up(pl->pt_off, hp.pt_off, s);
         up(pl->obs_img, hp.obs_img, s);
@@ -155,36 +154,45 @@ bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr
     PlanOpts po;
     po.force_dense = (ctx->flags & SFM_CTX_BA_DENSE_RCS) != 0;
     po.tile80 = (ctx->flags & SFM_CTX_BA_TILE80) != 0;
-    if (seed) {
-        if (!build_plan_grown(prob, *prev, seed->hp, h, po)) {
-            h.on_shard_ready = nullptr;
-            return false;
-        }
-    } else {
-        build_plan(prob, ctx->rank, ctx->world, h, po);
-    }
+    bool ok = true;
+    if (seed) ok = build_plan_grown(prob, *prev, seed->hp, h, po);
+    else build_plan(prob, ctx->rank, ctx->world, h, po);
     h.on_shard_ready = nullptr;
-    tm.mark(seed ? "build_plan_grown" : "build_plan");
+    if (ok) tm.mark(seed ? "build_plan_grown" : "build_plan");
+    return ok;
+}
+
+// The shard -> problem maps of points and observations on the device (pt_src,
+// src_off, obs_src): a grown plan gathers its measurements through them, the
+// plan cache's refresh every new value.
+void obs_source_map(sfm_ba_plan* pl, const sfm_ba_problem& prob) {
+    hipStream_t s = pl->ctx->stream;
+    const BAHostPlan& h = pl->hp;
+    std::vector<int32_t> ps(h.n_spt);
+    for (int64_t k = 0; k < h.n_spt; ++k) ps[k] = (int32_t)h.spt_global[k];
+    up(pl->pt_src, ps, s);
+    pl->src_off.alloc(prob.n_pt + 1);
+    pl->src_off.upload(prob.pt_offsets, prob.n_pt + 1, s);
+    pl->obs_src.alloc(h.n_sobs);
+    DBuf<int32_t> gperm;   // back to the context's cache, stream-ordered
+    if (!h.gobs_perm.empty()) up(gperm, h.gobs_perm, s);
+    ba_obs_source(pl->pt_src.p, pl->src_off.p, pl->pt_off.p, (int32_t)h.n_spt, (int32_t)h.n_cpt,
+                  h.gobs_perm.empty() ? nullptr : gperm.p, pl->obs_src.p, s);
+}
+
+// The plan's structure arrays to the device (and, a grown plan, the
+// measurements into shard order there).
+void upload_structure(sfm_ba_plan* pl, const sfm_ba_problem& prob, Staging& st, PhaseTimer& tm) {
+    hipStream_t s = pl->ctx->stream;
+    BAHostPlan& h = pl->hp;
     if (h.uv_on_device && h.n_sobs > 0) {
-        // the measurements into shard order on the device, through the
-        // shard -> problem maps the plan cache's refresh uses too
-        std::vector<int32_t> ps(h.n_spt);
-        for (int64_t k = 0; k < h.n_spt; ++k) ps[k] = (int32_t)h.spt_global[k];
-        up(pl->pt_src, ps, s);
-        pl->src_off.alloc(prob.n_pt + 1);
-        pl->src_off.upload(prob.pt_offsets, prob.n_pt + 1, s);
-        pl->obs_src.alloc(h.n_sobs);
-        DBuf<int32_t> gperm;   // back to the context's cache, stream-ordered
-        if (!h.gobs_perm.empty()) up(gperm, h.gobs_perm, s);
-        ba_obs_source(pl->pt_src.p, pl->src_off.p, pl->pt_off.p, (int32_t)h.n_spt, (int32_t)h.n_cpt,
-                      h.gobs_perm.empty() ? nullptr : gperm.p, pl->obs_src.p, s);
+        obs_source_map(pl, prob);
         pl->raw_uv.alloc(2 * (size_t)prob.n_obs);
         SFM_HIP(hipMemcpyAsync(pl->raw_uv.p, prob.obs_uv, 2 * (size_t)prob.n_obs * 8, hipMemcpyHostToDevice, s));
         pl->obs_uv.alloc(2 * (size_t)h.n_sobs);
         ba_gather_uv(pl->obs_src.p, pl->raw_uv.p, (int32_t)h.n_sobs, pl->obs_uv.p, s);
         tm.mark("gather_uv");
     }
-    Staging st;
     up(st, pl->chunks, h.chunks, s);
     up(st, pl->group_off, h.group_off, s);
     up(st, pl->img_obs_ptr, h.img_obs_ptr, s);
@@ -225,6 +233,16 @@ bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr
     up(st, pl->zbatch, h.zbatch, s);
     up(st, pl->zlong, h.zlong, s);
     up(pl->pterms, h.pterms, s);
+}
+
+// The solve's state: the initial values, the working points, the reduce
+// sources (SourceLayout; the terms arrive resolved against it), the RCS and
+// the scalars.
+void alloc_state(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr, const double* intr, const double* X,
+                 Staging& st) {
+    sfm_ctx* ctx = pl->ctx;
+    hipStream_t s = ctx->stream;
+    BAHostPlan& h = pl->hp;
     pl->Zbuf.alloc(h.n_z + 2);   // (+2: preduce's 16-byte pieces read one double past an odd block)
     HostVec<double> xs(3 * std::max<int64_t>(h.n_spt, 1));
     for (int64_t k = 0; k < h.n_spt; ++k)
@@ -243,17 +261,12 @@ bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr
     pl->scaleF.alloc(nF);
     // per-chunk Schur tiles and per-image Gram slices share one buffer so the
     // reduction terms address every source with a single offset
-    const size_t n_tiles = std::max<size_t>(h.n_group(), 1) * kTileR * kTileR;
-    const size_t fw = 6 + (size_t)h.iw;   // F columns of an image block
-    const size_t o_u = n_tiles, o_ub = o_u + fw * fw * (size_t)prob.n_img * kGramSeg,
-                 o_ucn = o_ub + fw * (size_t)prob.n_img * kGramSeg,
-                 n_gram = o_ucn + fw * (size_t)prob.n_img * kGramSeg;
-    pl->gram.alloc(n_gram);
+    const SourceLayout lay(h.n_group(), prob.n_img, h.iw);
+    pl->gram.alloc(lay.n_total);
     // the image blocks of images without observations in this shard are never
     // written (the Gram pass runs over the others) but may be reduce sources
     // (one rank: every image's U terms): zero once, they stay zero
-    SFM_HIP(hipMemsetAsync(pl->gram.p + o_u, 0, (n_gram - o_u) * sizeof(double), s));
-    // the terms arrive resolved against this buffer (build_plan, same layout)
+    SFM_HIP(hipMemsetAsync(pl->gram.p + lay.o_u, 0, (lay.n_total - lay.o_u) * sizeof(double), s));
     up(pl->terms, h.terms, s);
     // RCS: band + arrow + corner, or dense; the parts of a dense S no target
     // writes stay zero from here on
@@ -278,7 +291,12 @@ bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr
     pl->scal_h = static_cast<double*>(pinned_alloc((kScCount + 1) * sizeof(double)));
     std::memset(pl->scal_h, 0, (kScCount + 1) * sizeof(double));
     SFM_HIP(hipHostGetDevicePointer((void**)&pl->scal_dev, pl->scal_h, 0));
+}
 
+// DevProblem: the plan's sizes and the device arrays allocated so far (no HIP call)
+void bind_problem(sfm_ba_plan* pl, const sfm_ba_problem& prob) {
+    sfm_ctx* ctx = pl->ctx;
+    const BAHostPlan& h = pl->hp;
     DevProblem& P = pl->P;
     P.n_img = prob.n_img; P.n_intr = prob.n_intr;
     P.n_spt = (int32_t)h.n_spt; P.n_sobs = (int32_t)h.n_sobs;
@@ -322,6 +340,59 @@ bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr
     P.free_img = pl->free_img.p;
     P.targets = pl->targets.p; P.terms = pl->terms.p; P.n_targets = (int32_t)h.targets.size();
     P.n_zero = (int32_t)h.zero_targets.size();
+    const SourceLayout lay(h.n_group(), prob.n_img, h.iw);
+    P.scaleE = pl->scaleE.p; P.scaleF = pl->scaleF.p; P.tiles = pl->gram.p;
+    P.U = P.tiles + lay.o_u; P.Ub = P.tiles + lay.o_ub; P.Ucn = P.tiles + lay.o_ucn;
+    P.src = pl->gram.p;
+    P.Sband = pl->rcs.p;
+    P.Sarrow = P.Sband + h.n_sband;
+    P.Scorner = P.Sarrow + h.n_sarrow;
+    P.Sdense = P.Scorner + h.n_scorner;
+    P.rhs = P.Sdense + h.n_sdense;
+    P.bF = P.rhs + h.nF;
+    P.cnF = P.bF + h.nF;
+    P.Lcol = pl->Lcol.p; P.Larrow = pl->Larrow.p; P.zF = pl->zF.p; P.yF = pl->yF.p;
+    P.part_u = pl->part_u.p; P.part_s = pl->part_s.p;
+    P.scal = pl->scal.p;
+}
+
+// The long targets of one term list, [begin, end) of every target, longer
+// than `threshold`, in one buffer: [n target ids | n + 1 segment offsets |
+// n_seg (long index, first term)], and their segment partials.
+LongList long_list(sfm_ba_plan* pl, Staging& st, DBuf<int32_t>& buf, DBuf<double>& part,
+                   int32_t ReduceTarget::*begin, int32_t ReduceTarget::*end, int threshold) {
+    std::vector<int32_t> lt, off{0}, seg;
+    for (size_t t = 0; t < pl->hp.targets.size(); ++t) {
+        const ReduceTarget& T = pl->hp.targets[t];
+        const int32_t b0 = T.*begin, n = T.*end - b0;
+        if (n <= threshold) continue;
+        for (int32_t k = 0; k < n; k += kReduceSeg) {
+            seg.push_back((int32_t)lt.size());
+            seg.push_back(b0 + k);
+        }
+        lt.push_back((int32_t)t);
+        off.push_back((int32_t)(seg.size() / 2));
+    }
+    LongList L{};
+    L.n = (int32_t)lt.size();
+    L.n_seg = (int32_t)(seg.size() / 2);
+    std::vector<int32_t> all(lt);
+    all.insert(all.end(), off.begin(), off.end());
+    all.insert(all.end(), seg.begin(), seg.end());
+    up(st, buf, all, pl->ctx->stream);
+    L.targets = buf.p;
+    L.seg_off = L.targets + L.n;
+    L.seg = L.seg_off + L.n + 1;
+    part.alloc(36 * std::max<size_t>(L.n_seg, 1));
+    L.part = part.p;
+    return L;
+}
+
+// The reduce launches' shape: waves per target, split or fused, the long lists
+void reduce_launch_shape(sfm_ba_plan* pl, Staging& st) {
+    sfm_ctx* ctx = pl->ctx;
+    const BAHostPlan& h = pl->hp;
+    DevProblem& P = pl->P;
     {
         // reduce_kernel waves per target from the mean term count of the
         // targets it sums: C4 24 at N = 1, 50 at N = 4, 92 at N = 8
@@ -337,80 +408,31 @@ bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr
         P.red_waves = ctx->reduce_waves() ? ctx->reduce_waves() : mean >= 80 ? 4 : mean >= 40 ? 2 : 1;
         P.red_split = (ctx->flags & SFM_CTX_BA_SPLIT_REDUCE) ? 1 : 0;
     }
-    {
-        // long targets: [n_long targets | n_long+1 segment offsets | n_seg (long idx, term begin)]
-        std::vector<int32_t> lt, off{0}, seg;
-        for (size_t t = 0; t < h.targets.size(); ++t) {
-            const int32_t b0 = h.targets[t].c_begin, n = h.targets[t].c_end - b0;
-            if (n <= reduce_long_threshold()) continue;
-            for (int32_t k = 0; k < n; k += kReduceSeg) {
-                seg.push_back((int32_t)lt.size());
-                seg.push_back(b0 + k);
-            }
-            lt.push_back((int32_t)t);
-            off.push_back((int32_t)(seg.size() / 2));
-        }
-        P.n_long = (int32_t)lt.size();
-        P.n_lseg = (int32_t)(seg.size() / 2);
-        std::vector<int32_t> all(lt);
-        all.insert(all.end(), off.begin(), off.end());
-        all.insert(all.end(), seg.begin(), seg.end());
-        up(st, pl->long_targets, all, s);
-        P.long_targets = pl->long_targets.p;
-        P.lseg_off = P.long_targets + P.n_long;
-        P.lseg = P.lseg_off + P.n_long + 1;
-        pl->lpart.alloc(36 * std::max<size_t>(P.n_lseg, 1));
-        P.lpart = pl->lpart.p;
-        pl->lcount.alloc(std::max<size_t>(P.n_long, 1));
-        pl->lcount.zero(s);
-        P.lcount = pl->lcount.p;
-    }
-    {
-        // the same for long product-term lists (general points)
-        std::vector<int32_t> lt, off{0}, seg;
-        for (size_t t = 0; t < h.targets.size(); ++t) {
-            const int32_t b0 = h.targets[t].p_begin, n = h.targets[t].p_end - b0;
-            if (n <= preduce_long_threshold()) continue;
-            for (int32_t k = 0; k < n; k += kReduceSeg) {
-                seg.push_back((int32_t)lt.size());
-                seg.push_back(b0 + k);
-            }
-            lt.push_back((int32_t)t);
-            off.push_back((int32_t)(seg.size() / 2));
-        }
-        P.n_plong = (int32_t)lt.size();
-        P.n_plseg = (int32_t)(seg.size() / 2);
-        std::vector<int32_t> all(lt);
-        all.insert(all.end(), off.begin(), off.end());
-        all.insert(all.end(), seg.begin(), seg.end());
-        up(st, pl->plong_targets, all, s);
-        P.plong_targets = pl->plong_targets.p;
-        P.plseg_off = P.plong_targets + P.n_plong;
-        P.plseg = P.plseg_off + P.n_plong + 1;
-        pl->plpart.alloc(36 * std::max<size_t>(P.n_plseg, 1));
-        P.plpart = pl->plpart.p;
-    }
-    P.scaleE = pl->scaleE.p; P.scaleF = pl->scaleF.p; P.tiles = pl->gram.p;
-    P.U = P.tiles + o_u; P.Ub = P.tiles + o_ub; P.Ucn = P.tiles + o_ucn;
-    P.src = pl->gram.p;
-    P.Sband = pl->rcs.p;
-    P.Sarrow = P.Sband + h.n_sband;
-    P.Scorner = P.Sarrow + h.n_sarrow;
-    P.Sdense = P.Scorner + h.n_scorner;
-    P.rhs = P.Sdense + h.n_sdense;
-    P.bF = P.rhs + h.nF;
-    P.cnF = P.bF + h.nF;
-    P.Lcol = pl->Lcol.p; P.Larrow = pl->Larrow.p; P.zF = pl->zF.p; P.yF = pl->yF.p;
+    P.lsum = long_list(pl, st, pl->long_targets, pl->lpart, &ReduceTarget::c_begin, &ReduceTarget::c_end,
+                       reduce_long_threshold());
+    pl->lcount.alloc(std::max<size_t>(P.lsum.n, 1));
+    pl->lcount.zero(ctx->stream);
+    P.lcount = pl->lcount.p;
+    // the same for long product-term lists (general points)
+    P.lprod = long_list(pl, st, pl->plong_targets, pl->plpart, &ReduceTarget::p_begin, &ReduceTarget::p_end,
+                        preduce_long_threshold());
+}
+
+// The RCS solver: the sequential band solver's window, the step and finalize
+// partials, then block cyclic reduction (BCR) or the dense dataflow solve
+void setup_rcs_solver(sfm_ba_plan* pl) {
+    sfm_ctx* ctx = pl->ctx;
+    hipStream_t s = ctx->stream;
+    const BAHostPlan& h = pl->hp;
+    DevProblem& P = pl->P;
     if (!h.dense) {
         bool lds = true;
         solve_lds_bytes(P, &lds);
         if (!lds) pl->Wg.alloc(solve_window_doubles(P));
     }
     P.Wglobal = pl->Wg.p;
-    P.part_u = pl->part_u.p; P.part_s = pl->part_s.p;
     pl->part_t.alloc((size_t)kPartT * std::max(ba_step_blocks(P), 1));
     P.part_t = pl->part_t.p;
-    P.scal = pl->scal.p;
     pl->fin_part.alloc(16 * 12);
     pl->fin_count.alloc(1);
     pl->fin_count.zero(s);
@@ -472,12 +494,30 @@ bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr
         }
     }
     if (std::getenv("SFM_SCHUR_STAMPS")) pl->stamps.alloc(6 * std::max<size_t>(h.chunks.size(), 1));
+}
+
+// The plan of a problem: from scratch, or -- seed set (sfm_ba_solve's plan
+// cache, a problem grown from the previous call's, GrowPrev) -- grown from
+// the seed plan (build_plan_grown: the same arrays; the measurements are
+// gathered into shard order on the device).  Returns false, with nothing
+// done and the seed intact, when the seed cannot seed this problem.
+bool create_plan(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* extr, const double* intr,
+                 const double* X, sfm_ba_plan* seed = nullptr, const GrowPrev* prev = nullptr) {
+    PhaseTimer tm("create_plan");
+    if (!plan_host(pl, prob, seed, prev, tm)) return false;
+    Staging st;   // (its blocks stay until the stream's sync below)
+    upload_structure(pl, prob, st, tm);
+    alloc_state(pl, prob, extr, intr, X, st);
+    bind_problem(pl, prob);
+    reduce_launch_shape(pl, st);
+    setup_rcs_solver(pl);
     tm.mark("alloc+upload");
-    SFM_HIP(hipStreamSynchronize(s));
+    SFM_HIP(hipStreamSynchronize(pl->ctx->stream));
     // the observation staging goes back to the cache (the uploads are done);
     // a plan that can seed a grown one keeps its shard arrays (obs_img,
     // obs_slot and the reduce plan's terms: build_plan_grown takes their
     // unchanged prefix)
+    BAHostPlan& h = pl->hp;
     if (!(h.grow.ok && cache_enabled_for_growth())) {
         h.obs_img = HostVec<int32_t>();
         h.obs_slot = HostVec<int32_t>();
@@ -502,16 +542,7 @@ void refresh_values(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* e
     BAHostPlan& h = pl->hp;
     PhaseTimer tm("refresh_values");
     if (!pl->obs_src.p && h.n_sobs > 0) {
-        std::vector<int32_t> ps(h.n_spt);
-        for (int64_t k = 0; k < h.n_spt; ++k) ps[k] = (int32_t)h.spt_global[k];
-        up(pl->pt_src, ps, s);
-        pl->src_off.alloc(prob.n_pt + 1);
-        pl->src_off.upload(prob.pt_offsets, prob.n_pt + 1, s);
-        pl->obs_src.alloc(h.n_sobs);
-        DBuf<int32_t> gperm;   // back to the context's cache, stream-ordered
-        if (!h.gobs_perm.empty()) up(gperm, h.gobs_perm, s);
-        ba_obs_source(pl->pt_src.p, pl->src_off.p, pl->pt_off.p, (int32_t)h.n_spt, (int32_t)h.n_cpt,
-                      h.gobs_perm.empty() ? nullptr : gperm.p, pl->obs_src.p, s);
+        obs_source_map(pl, prob);
         tm.mark("maps");
     }
     if (h.n_sobs > 0) {

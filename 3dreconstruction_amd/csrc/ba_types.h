@@ -53,6 +53,23 @@ constexpr int kIntrSlots = 4;             // staged intrinsics blocks per chunk
 constexpr int kZMaxDoubles = 18432;       // LDS Z accumulator of one general point (144 KB):
                                           // ~1000 parameter blocks per point
 
+// The solver's one reduce-source buffer, in doubles: [chunk tiles | U | Ub | Ucn],
+// one 80x80 tile per tile group (at least one), then per image and Gram
+// workgroup an fw x fw block U and the fw-vectors Ub and Ucn (fw = 6 + the
+// intrinsics width).  Every FlatTerm.off of a plan is an offset into it: the
+// planner resolves its terms against this layout, a grown plan patches its
+// seed's offsets by the difference of two of them, and the solver allocates
+// and binds the buffer from it.
+struct SourceLayout {
+    int64_t fw, o_u, o_ub, o_ucn, n_total;
+    SourceLayout(int64_t n_group, int64_t n_img, int32_t iw) : fw(6 + iw) {
+        o_u = (n_group > 1 ? n_group : 1) * kTileR * kTileR;
+        o_ub = o_u + fw * fw * n_img * kGramSeg;
+        o_ucn = o_ub + fw * n_img * kGramSeg;
+        n_total = o_ucn + fw * n_img * kGramSeg;
+    }
+};
+
 // Per-camera precomputed rotation terms (for current or candidate params).
 //   Rodrigues branch: P = X c + (u x X) s + u (u.X)(1-c) + t,
 //                     dP/dX = R, dP/dw = -R [X]x Ar  (Ar = (w w' + (R'-I)[w]x)/|w|^2)
