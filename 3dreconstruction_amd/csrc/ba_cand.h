@@ -1,5 +1,5 @@
 // Device arithmetic of the LM candidate (x + delta) shared by cand_kernel
-// (ba_kernels.hip) and the BCR back substitution, which forms its blocks'
+// (ba_step.hip) and the BCR back substitution, which forms its blocks'
 // camera candidates as soon as their y is known (ba_bcr.hip): the per-camera
 // precompute and the per-column step, one definition so both give the same
 // bits per element.

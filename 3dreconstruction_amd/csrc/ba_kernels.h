@@ -1,5 +1,8 @@
-// Launch wrappers for the BA kernels (ba_kernels.hip), called by the LM
-// driver (ba_solver.cpp).
+// Launch wrappers for the BA kernels, called by the LM driver (ba_solver.cpp);
+// one file per pass: ba_gram.hip (ba_campre, ba_image_gram, ba_gram_rescale,
+// ba_fscale, ba_fill, ba_segs), ba_schur.hip (ba_schur), ba_reduce.hip
+// (ba_reduce), ba_step.hip (ba_solve, ba_cand, ba_step, ba_finalize,
+// ba_publish_gathered); shared device helpers in ba_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,6 @@
 // Types shared by the BA host planner (ba_plan.cpp), the LM driver
-// (ba_solver.cpp) and the gfx950 kernels (ba_kernels.hip).
+// (ba_solver.cpp) and the gfx950 kernels (ba_gram / ba_schur / ba_reduce /
+// ba_step .hip).
 //
 // HBM layout (DESIGN.md §BA data layout), per rank:
 //   points   : X[3*n_spt] in shard order (landmark-major, sorted by first
