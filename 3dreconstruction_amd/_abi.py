@@ -130,6 +130,17 @@ class BAPlanShape(C.Structure):
                 ("n_targets", C.c_int64), ("n_terms", C.c_int64), ("n_pterms", C.c_int64)]
 
 
+class BAWashOpts(C.Structure):
+    _fields_ = [("max_residual_px", C.c_double), ("min_angle_deg", C.c_double),
+                ("min_track_len", C.c_int32), ("cheirality", C.c_int32)]
+
+
+class BAWashStats(C.Structure):
+    _fields_ = [("n_obs_depth", C.c_int64), ("n_obs_residual", C.c_int64),
+                ("n_pt_short", C.c_int64), ("n_pt_angle", C.c_int64),
+                ("n_obs_kept", C.c_int64), ("n_pt_kept", C.c_int64)]
+
+
 class SynthBAConfig(C.Structure):
     _fields_ = [("n_cam", C.c_int32), ("k", C.c_int32), ("vis_mode", C.c_int32),
                 ("n_intr", C.c_int32), ("n_pt", C.c_int64), ("seed", C.c_uint64),
@@ -242,6 +253,13 @@ SIGNATURES = [
     ("sfm_ba_plan_destroy", C.c_int, [C.c_void_p]),
     ("sfm_ba_plan_get_info", C.c_int, [C.c_void_p, C.POINTER(BAPlanInfo)]),
     ("sfm_ba_plan_get_trace", C.c_int, [C.c_void_p, C.POINTER(BAIter), C.c_int32, i32p]),
+    ("sfm_ba_wash_default_options", None, [C.POINTER(BAWashOpts)]),
+    ("sfm_ba_wash", C.c_int, [C.c_void_p, C.POINTER(BAProblem), f64p, f64p, f64p, C.POINTER(BAWashOpts),
+                              f64p, f64p, u8p, u8p, C.POINTER(BAWashStats)]),
+    ("sfm_ba_plan_wash", C.c_int, [C.c_void_p, C.POINTER(BAWashOpts), f64p, f64p, u8p, u8p,
+                                   C.POINTER(BAWashStats)]),
+    ("sfm_ba_plan_wash_last_ms", C.c_int, [C.c_void_p, f64p, f64p]),
+    ("sfm_ba_wash_apply", C.c_int, [C.POINTER(BAProblem), f64p, u8p, u8p, i64p, i32p, f64p, f64p, i64p]),
     ("sfm_ba_intr_width", C.c_int, [C.c_int32]),
     ("sfm_ba_partition", C.c_int, [C.POINTER(BAProblem), C.c_int32, i64p, i64p]),
     ("sfm_ba_describe", C.c_int, [C.POINTER(BAProblem), C.c_int32, C.c_int32, C.POINTER(BAPlanShape)]),

@@ -301,6 +301,25 @@ class BAPlan:
                                                  abi.ptr(x, abi.f64p)), "sfm_ba_plan_download")
         return e, i, x
 
+    def wash(self, opts=None):
+        """sfm_ba_plan_wash at the plan's current parameters: dict(residual
+        [n_obs, 2], max_angle [n_pt], keep_obs, keep_pt (bool), stats), in the
+        problem's own order."""
+        pr = self._keep[0]
+        out = _wash_outputs(pr.n_obs, pr.n_pt)
+        st = abi.BAWashStats()
+        _check(self.ctx.lib.sfm_ba_plan_wash(self.h, C.byref(opts) if opts is not None else None,
+                                             *_wash_ptrs(out), C.byref(st)), "sfm_ba_plan_wash")
+        return _wash_result(out, st)
+
+    def wash_last_ms(self):
+        """(observation pass, point pass) device ms of the last wash(); -1
+        unless the context was created with SFM_CTX_TIME_KERNELS."""
+        a, b = C.c_double(), C.c_double()
+        _check(self.ctx.lib.sfm_ba_plan_wash_last_ms(self.h, C.byref(a), C.byref(b)),
+               "sfm_ba_plan_wash_last_ms")
+        return a.value, b.value
+
     def info(self):
         inf = abi.BAPlanInfo()
         _check(self.ctx.lib.sfm_ba_plan_get_info(self.h, C.byref(inf)), "sfm_ba_plan_get_info")
@@ -333,6 +352,74 @@ def ba_solve(ctx, problem, extr, intr, X, opts=None):
                               abi.ptr(intr, abi.f64p), abi.ptr(X, abi.f64p), C.byref(o),
                               C.byref(s))
     return rc, s
+
+
+def ba_wash_default_options():
+    o = abi.BAWashOpts()
+    abi.load().sfm_ba_wash_default_options(C.byref(o))
+    return o
+
+
+def _wash_outputs(n_obs, n_pt):
+    return (np.zeros(2 * max(n_obs, 1)), np.zeros(max(n_pt, 1)), np.zeros(max(n_obs, 1), np.uint8),
+            np.zeros(max(n_pt, 1), np.uint8), n_obs, n_pt)
+
+
+def _wash_ptrs(out):
+    r, a, ko, kp = out[:4]
+    return abi.ptr(r, abi.f64p), abi.ptr(a, abi.f64p), abi.ptr(ko, abi.u8p), abi.ptr(kp, abi.u8p)
+
+
+def _wash_result(out, st):
+    r, a, ko, kp, n_obs, n_pt = out
+    return dict(residual=r[:2 * n_obs].reshape(-1, 2), max_angle=a[:n_pt], keep_obs=ko[:n_obs].astype(bool),
+                keep_pt=kp[:n_pt].astype(bool), stats={f: getattr(st, f) for f, _ in abi.BAWashStats._fields_})
+
+
+def ba_wash(ctx, problem, extr, intr, X, opts=None):
+    """sfm_ba_wash (post-BA outlier rejection) at (extr, intr, X):
+    dict(residual [n_obs, 2], max_angle [n_pt] in degrees, keep_obs, keep_pt
+    (bool), stats), in the problem's own order.  opts: BAWashOpts (None: the
+    defaults, ba_wash_default_options())."""
+    out = _wash_outputs(problem.n_obs, problem.n_pt)
+    st = abi.BAWashStats()
+    _check(ctx.lib.sfm_ba_wash(ctx.h, C.byref(problem), abi.ptr(extr, abi.f64p), abi.ptr(intr, abi.f64p),
+                               abi.ptr(X, abi.f64p), C.byref(opts) if opts is not None else None,
+                               *_wash_ptrs(out), C.byref(st)), "sfm_ba_wash")
+    return _wash_result(out, st)
+
+
+def ba_wash_apply(problem, X, keep_obs, keep_pt):
+    """[cpu] sfm_ba_wash_apply: (washed BAProblem, X of its points, pt_map).
+    The new problem keeps its arrays alive and shares img_intr with `problem`,
+    which has to outlive it."""
+    lib = abi.load()
+    ko = np.ascontiguousarray(keep_obs, np.uint8)
+    kp = np.ascontiguousarray(keep_pt, np.uint8)
+    X = np.ascontiguousarray(X, np.float64)
+    if len(ko) != problem.n_obs or len(kp) != problem.n_pt or len(X) != 3 * problem.n_pt:
+        raise ValueError("ba_wash_apply: mask / X sizes do not match the problem")
+    # the sizes the wash's stats give (the library writes the kept observations of kept points only,
+    # and rejects a kept observation of a removed point)
+    n_pt = int(np.count_nonzero(kp))
+    n_obs = int(np.count_nonzero(ko))
+    off = np.zeros(n_pt + 1, np.int64)
+    img = np.zeros(max(n_obs, 1), np.int32)
+    uv = np.zeros(2 * max(n_obs, 1))
+    Xo = np.zeros(3 * max(n_pt, 1))
+    pm = np.zeros(max(n_pt, 1), np.int64)
+    _check(lib.sfm_ba_wash_apply(C.byref(problem), abi.ptr(X, abi.f64p), abi.ptr(ko, abi.u8p), abi.ptr(kp, abi.u8p),
+                                 abi.ptr(off, abi.i64p), abi.ptr(img, abi.i32p), abi.ptr(uv, abi.f64p),
+                                 abi.ptr(Xo, abi.f64p), abi.ptr(pm, abi.i64p)), "sfm_ba_wash_apply")
+    pr = abi.BAProblem()
+    pr.n_img, pr.n_intr, pr.n_pt, pr.n_obs = problem.n_img, problem.n_intr, n_pt, n_obs
+    pr.pt_offsets = abi.ptr(off, abi.i64p)
+    pr.obs_img = abi.ptr(img, abi.i32p)
+    pr.obs_uv = abi.ptr(uv, abi.f64p)
+    pr.img_intr = problem.img_intr
+    pr.const_img, pr.camera_model, pr.huber_a = problem.const_img, problem.camera_model, problem.huber_a
+    pr._keep = (off, img, uv, problem)
+    return pr, Xo[:3 * n_pt], pm[:n_pt]
 
 
 def ba_cache_stats(ctx):

@@ -367,8 +367,6 @@ bool chunkable(const sfm_ba_problem& P, const BAHostPlan& pl, int64_t p) {
 
 }  // namespace
 
-namespace {
-
 void validate_problem(const sfm_ba_problem& P) {
     SFM_REQUIRE(P.n_img >= 1 && P.n_intr >= 1 && P.n_pt >= 0 && P.n_obs >= 0 &&
                     P.pt_offsets && (P.n_obs == 0 || (P.obs_img && P.obs_uv)) && P.img_intr,
@@ -400,6 +398,8 @@ void validate_problem(const sfm_ba_problem& P) {
     SFM_REQUIRE(sfm_ba_intr_width(P.camera_model) > 0, SFM_ERR_INVALID_ARG, "unknown camera_model %d",
                 P.camera_model);
 }
+
+namespace {
 
 // RCS storage and solver, identical on every rank: the block-banded form
 // (block cyclic reduction, ba_bcr.hip) for a camera band of <= 10 blocks

@@ -129,6 +129,10 @@ struct PlanOpts {
     bool tile80 = false;
 };
 
+// The argument checks of every entry point that takes a problem (build_plan's;
+// sfm_ba_wash, sfm_ba_wash_apply).  Throws SfmError.
+void validate_problem(const sfm_ba_problem& prob);
+
 // Validates the problem and fills every field.  Throws SfmError.
 void build_plan(const sfm_ba_problem& prob, int rank, int world, BAHostPlan& plan, const PlanOpts& opts = {});
 

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <vector>
 #include <unordered_map>
 #include <thread>
@@ -32,6 +33,7 @@
 #include "ba_kernels.h"
 #include "ba_order.h"
 #include "ba_plan.h"
+#include "ba_wash.h"
 #include "common.h"
 #include "../include/sfm/pool.hpp"
 
@@ -88,6 +90,11 @@ struct sfm_ba_plan {
     double schur_ms_total = 0;
     int64_t schur_launches = 0;
     bool cur_is_a = true;
+    // sfm_ba_plan_wash: results, scratch and the parameters' CamPre, from the
+    // first wash on (nothing of it at plan creation)
+    std::unique_ptr<WashBuffers> wash;
+    DBuf<CamPre> wash_cp;
+    double wash_ms[2] = {-1.0, -1.0};
     ~sfm_ba_plan() {
         if (scal_h) pinned_free(scal_h);
     }
@@ -165,14 +172,14 @@ bool plan_host(sfm_ba_plan* pl, const sfm_ba_problem& prob, sfm_ba_plan* seed, c
 // The shard -> problem maps of points and observations on the device (pt_src,
 // src_off, obs_src): a grown plan gathers its measurements through them, the
 // plan cache's refresh every new value.
-void obs_source_map(sfm_ba_plan* pl, const sfm_ba_problem& prob) {
+void obs_source_map(sfm_ba_plan* pl, const int64_t* pt_offsets, int64_t n_pt) {
     hipStream_t s = pl->ctx->stream;
     const BAHostPlan& h = pl->hp;
     std::vector<int32_t> ps(h.n_spt);
     for (int64_t k = 0; k < h.n_spt; ++k) ps[k] = (int32_t)h.spt_global[k];
     up(pl->pt_src, ps, s);
-    pl->src_off.alloc(prob.n_pt + 1);
-    pl->src_off.upload(prob.pt_offsets, prob.n_pt + 1, s);
+    pl->src_off.alloc(n_pt + 1);
+    pl->src_off.upload(pt_offsets, n_pt + 1, s);
     pl->obs_src.alloc(h.n_sobs);
     DBuf<int32_t> gperm;   // back to the context's cache, stream-ordered
     if (!h.gobs_perm.empty()) up(gperm, h.gobs_perm, s);
@@ -186,7 +193,7 @@ void upload_structure(sfm_ba_plan* pl, const sfm_ba_problem& prob, Staging& st, 
     hipStream_t s = pl->ctx->stream;
     BAHostPlan& h = pl->hp;
     if (h.uv_on_device && h.n_sobs > 0) {
-        obs_source_map(pl, prob);
+        obs_source_map(pl, prob.pt_offsets, prob.n_pt);
         pl->raw_uv.alloc(2 * (size_t)prob.n_obs);
         SFM_HIP(hipMemcpyAsync(pl->raw_uv.p, prob.obs_uv, 2 * (size_t)prob.n_obs * 8, hipMemcpyHostToDevice, s));
         pl->obs_uv.alloc(2 * (size_t)h.n_sobs);
@@ -542,7 +549,7 @@ void refresh_values(sfm_ba_plan* pl, const sfm_ba_problem& prob, const double* e
     BAHostPlan& h = pl->hp;
     PhaseTimer tm("refresh_values");
     if (!pl->obs_src.p && h.n_sobs > 0) {
-        obs_source_map(pl, prob);
+        obs_source_map(pl, prob.pt_offsets, prob.n_pt);
         tm.mark("maps");
     }
     if (h.n_sobs > 0) {
@@ -883,7 +890,76 @@ void download(sfm_ba_plan* pl, double* extr, double* intr, double* X) {
     }
 }
 
+// The wash at the plan's current parameters, on its shard arrays (world 1: the
+// whole problem in sorted order); the kernels scatter through the shard ->
+// problem maps (pt_src, obs_src: spt_global and, for general points re-sorted
+// by image, gobs_perm), built here on the first call unless the plan cache's
+// refresh already did.
+void wash_plan(sfm_ba_plan* pl, const sfm_ba_wash_opts& O) {
+    sfm_ctx* ctx = pl->ctx;
+    hipStream_t s = ctx->stream;
+    const BAHostPlan& h = pl->hp;
+    if (!pl->wash) {
+        auto b = std::make_unique<WashBuffers>();
+        b->alloc(h.n_spt, h.n_sobs);
+        pl->wash_cp.alloc(h.n_img);
+        pl->wash = std::move(b);
+    }
+    std::vector<int64_t> off;   // (lives until the upload is done: the sync below)
+    if (!pl->obs_src.p && h.n_sobs > 0) {
+        // the problem's pt_offsets from the shard's: a point keeps its observation count
+        off.assign((size_t)h.n_pt + 1, 0);
+        for (int64_t k = 0; k < h.n_spt; ++k) off[h.spt_global[k] + 1] = h.pt_off[k + 1] - h.pt_off[k];
+        for (int64_t p = 0; p < h.n_pt; ++p) off[p + 1] += off[p];
+        obs_source_map(pl, off.data(), h.n_pt);
+        SFM_HIP(hipStreamSynchronize(s));
+    } else if (!pl->pt_src.p && h.n_spt > 0) {   // points only (no observations)
+        std::vector<int32_t> ps(h.n_spt);
+        for (int64_t k = 0; k < h.n_spt; ++k) ps[k] = (int32_t)h.spt_global[k];
+        up(pl->pt_src, ps, s);
+        SFM_HIP(hipStreamSynchronize(s));
+    }
+    const bool ran = !pl->trace.empty();
+    const double* e = !ran ? pl->extr0.p : pl->cur_is_a ? pl->ea.p : pl->eb.p;
+    const double* in = !ran ? pl->intr0.p : pl->cur_is_a ? pl->ia.p : pl->ib.p;
+    const double* x = !ran ? pl->X0.p : pl->cur_is_a ? pl->Xa.p : pl->Xb.p;
+    ba_campre(e, h.n_img, pl->wash_cp.p, s);
+    WashInput W;
+    W.n_pt = (int32_t)h.n_spt; W.n_obs = (int32_t)h.n_sobs;
+    W.cam_model = pl->P.cam_model; W.iw = h.iw;
+    W.pt_off = pl->pt_off.p; W.obs_img = pl->obs_img.p; W.obs_uv = pl->obs_uv.p; W.img_intr = pl->img_intr.p;
+    W.cp = pl->wash_cp.p; W.intr = in; W.X = x;
+    W.pt_map = pl->pt_src.p; W.obs_map = pl->obs_src.p;
+    const bool timed = ctx->time_kernels;
+    ba_wash_eval(W, O, *pl->wash, s, timed ? ctx_events(ctx) : nullptr, timed ? pl->wash_ms : nullptr);
+}
+
 }  // namespace
+
+extern "C" int sfm_ba_plan_wash(sfm_ba_plan* pl, const sfm_ba_wash_opts* opts, double* residual,
+                                double* max_angle_deg, uint8_t* keep_obs, uint8_t* keep_pt,
+                                sfm_ba_wash_stats* stats) {
+    return guarded([&] {
+        const sfm_ba_wash_opts O = wash_options(opts);
+        SFM_REQUIRE(pl, SFM_ERR_INVALID_ARG, "null plan");
+        SFM_REQUIRE(pl->ctx->world == 1, SFM_ERR_UNSUPPORTED,
+                    "sfm_ba_plan_wash on a sharded plan (world_size %d): a shard holds only its own points; "
+                    "use sfm_ba_wash", pl->ctx->world);
+        CtxScope scope_(pl->ctx);
+        wash_plan(pl, O);
+        ba_wash_download(*pl->wash, residual, max_angle_deg, keep_obs, keep_pt, stats, pl->ctx->stream);
+        return SFM_OK;
+    });
+}
+
+extern "C" int sfm_ba_plan_wash_last_ms(sfm_ba_plan* pl, double* obs_ms, double* point_ms) {
+    return guarded([&] {
+        SFM_REQUIRE(pl, SFM_ERR_INVALID_ARG, "null plan");
+        if (obs_ms) *obs_ms = pl->wash_ms[0];
+        if (point_ms) *point_ms = pl->wash_ms[1];
+        return SFM_OK;
+    });
+}
 
 extern "C" void sfm_ba_default_options(sfm_ba_options* o) {
     if (!o) return;

@@ -1,0 +1,392 @@
+// Post-BA outlier rejection for CDNA4 (gfx950), fp64: the filter OpenMVG's
+// engine runs after every bundle adjustment (badTrackRejector:
+// RemoveOutliers_PixelResidualError, then RemoveOutliers_AngleError) and the
+// reference left as a hook (src/adjuster/BundleAdjuster.h:179-184, washPoint()).
+//
+//   obs pass    one lane per observation: P = R X + t, the unweighted residual of
+//               the problem's camera model (the solver's projection formulas),
+//               the depth / residual reject code and the ray R' P.  Streaming:
+//               reads image 4 B + measurement 16 B, writes residual 16 B + code
+//               1 B + ray 24 B per observation (the cameras and points it gathers
+//               are shared by neighbouring lanes).
+//   point pass  survivors, the short-track rule and the largest angle between two
+//               surviving rays, in one pass: a point of <= kWashGroup
+//               observations takes a lane group (64 / kWashGroup points per
+//               wave), a longer one a whole wave, all pairs in rounds of 64.
+//               The widest pair is chosen by comparing (|a x b|, a.b) tuples;
+//               one atan2 per point.
+//
+// Both write their results through kernel-order -> caller-order maps (a plan's
+// shard order; null for arrays already in caller order).  The counters are
+// integer block sums added with integer atomics: the same numbers every run.
+#include "ba_device.h"
+#include "ba_wash.h"
+
+namespace sfm {
+namespace {
+
+constexpr int kObsThreads = 256;
+constexpr int kWin = kObsThreads + 2;   // pt_off window of an observation block: its points and their end
+constexpr int kPtThreads = 256;
+constexpr int kPtPerWave = 64 / kWashGroup;
+
+// P = R X + t and the unweighted residual (r0, r1): linearize()'s projection
+// (ba_device.h) without the loss and the Jacobians, formula for formula, so
+// this is the residual the solver squares.
+template <int CM>
+__device__ __forceinline__ void wash_project(const CamPre& cp, const double* in, const double* X, double u0,
+                                             double u1, double (&P)[3], double& r0, double& r1) {
+    const double* u = cp.u;
+    const double cr0 = u[1] * X[2] - u[2] * X[1], cr1 = u[2] * X[0] - u[0] * X[2],
+                 cr2 = u[0] * X[1] - u[1] * X[0];
+    if (cp.small != 0.0) {
+        P[0] = X[0] + cr0; P[1] = X[1] + cr1; P[2] = X[2] + cr2;
+    } else {
+        const double tmp = (u[0] * X[0] + u[1] * X[1] + u[2] * X[2]) * cp.omc;
+        P[0] = X[0] * cp.c + cr0 * cp.s + u[0] * tmp;
+        P[1] = X[1] * cp.c + cr1 * cp.s + u[1] * tmp;
+        P[2] = X[2] * cp.c + cr2 * cp.s + u[2] * tmp;
+    }
+    P[0] += cp.t[0]; P[1] += cp.t[1]; P[2] += cp.t[2];
+    const double iz = rcp_nr(P[2]);
+    if constexpr (CM == SFM_CAM_RADIAL3) {
+        const double xu = P[0] * iz, yu = P[1] * iz;
+        const double r2 = xu * xu + yu * yu, r4 = r2 * r2, r6 = r4 * r2;
+        const double rc = 1.0 + in[3] * r2 + in[4] * r4 + in[5] * r6;
+        r0 = in[1] + in[0] * (xu * rc) - u0;
+        r1 = in[2] + in[0] * (yu * rc) - u1;
+    } else if constexpr (CM == SFM_CAM_SNAVELY) {
+        const double xp = -P[0] * iz, yp = -P[1] * iz;
+        const double r2 = xp * xp + yp * yp;
+        const double d = 1.0 + r2 * (in[1] + in[2] * r2);
+        r0 = in[0] * d * xp - u0;
+        r1 = in[0] * d * yp - u1;
+    } else {
+        const double x = P[0] * iz, y = P[1] * iz;
+        r0 = in[0] * x + in[2] - u0;
+        r1 = in[1] * y + in[3] - u1;
+    }
+}
+
+// blk_pt[b] = the point owning observation b * kObsThreads (one lane per point)
+__global__ __launch_bounds__(256) void wash_block_point_kernel(const int32_t* __restrict__ pt_off, int32_t n_pt,
+                                                              int32_t* __restrict__ blk_pt) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_pt) return;
+    const int64_t a = pt_off[k], b = pt_off[k + 1];
+    for (int64_t blk = (a + kObsThreads - 1) / kObsThreads; blk * kObsThreads < b; ++blk) blk_pt[blk] = (int32_t)k;
+}
+
+template <int CM>
+__global__ __launch_bounds__(kObsThreads) void wash_obs_kernel(WashInput in, double max_res, int cheirality,
+                                                               const int32_t* __restrict__ blk_pt,
+                                                               double2* __restrict__ residual,
+                                                               uint8_t* __restrict__ code, double* __restrict__ ray,
+                                                               unsigned long long* __restrict__ counts) {
+    __shared__ int32_t win[kWin];
+    __shared__ unsigned cnt[2];
+    const int tid = threadIdx.x;
+    const int64_t s = (int64_t)blockIdx.x * kObsThreads + tid;
+    const int32_t p0 = blk_pt[blockIdx.x];
+    for (int i = tid; i < kWin; i += kObsThreads) win[i] = in.pt_off[min((int64_t)p0 + i, (int64_t)in.n_pt)];
+    if (tid < 2) cnt[tid] = 0;
+    __syncthreads();
+    uint8_t cd = kWashKeep;
+    const bool live = s < in.n_obs;
+    if (live) {
+        // the observation's point: the last one of the window starting at or before s
+        int lo = 0, hi = kWin - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (win[mid] <= s) lo = mid; else hi = mid - 1;
+        }
+        int32_t p = p0 + lo;
+        if (lo == kWin - 1) {   // a run of points without observations longer than the window
+            int32_t l = p, h = in.n_pt - 1;
+            while (l < h) {
+                const int32_t mid = l + (h - l + 1) / 2;
+                if (in.pt_off[mid] <= s) l = mid; else h = mid - 1;
+            }
+            p = l;
+        }
+        const int32_t img = in.obs_img[s];
+        const CamPre& cp = in.cp[img];
+        const double* ib = in.intr + (int64_t)in.iw * in.img_intr[img];
+        const double* Xp = in.X + 3 * (int64_t)p;
+        const double X[3] = {Xp[0], Xp[1], Xp[2]};
+        const double2 uv = reinterpret_cast<const double2*>(in.obs_uv)[s];
+        double P[3], r0, r1;
+        wash_project<CM>(cp, ib, X, uv.x, uv.y, P, r0, r1);
+        const bool front = CM == SFM_CAM_SNAVELY ? P[2] < 0.0 : P[2] > 0.0;
+        if (!(isfinite(r0) && isfinite(r1)) || (cheirality != 0 && !front)) cd = kWashDepth;
+        else if (max_res > 0.0 && sqrt(r0 * r0 + r1 * r1) > max_res) cd = kWashResidual;
+        const int64_t so = in.obs_map ? in.obs_map[s] : s;
+        residual[so] = make_double2(r0, r1);
+        code[s] = cd;
+        // the ray from the camera centre to the point in world axes, R' P
+        double* d = ray + 3 * s;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) d[j] = cp.R[j] * P[0] + cp.R[3 + j] * P[1] + cp.R[6 + j] * P[2];
+    }
+    const unsigned long long md = __ballot(cd == kWashDepth), mr = __ballot(cd == kWashResidual);
+    if ((tid & 63) == 0) {
+        if (md) atomicAdd(&cnt[0], (unsigned)__popcll(md));
+        if (mr) atomicAdd(&cnt[1], (unsigned)__popcll(mr));
+    }
+    __syncthreads();
+    if (tid < 2 && cnt[tid]) atomicAdd(&counts[tid == 0 ? kWcObsDepth : kWcObsResidual], (unsigned long long)cnt[tid]);
+}
+
+// The widest pair so far as (|a x b|, a.b): the angle is atan2(s, c).
+struct Widest {
+    double s, c;
+};
+// angle(s1, c1) > angle(s2, c2), both in [0, pi]: the sign of sin(t1 - t2);
+// opposite against parallel rays (both sines 0) by the cosine
+__device__ __forceinline__ bool wider(double s1, double c1, double s2, double c2) {
+    const double det = s1 * c2 - c1 * s2;
+    return det > 0.0 || (det == 0.0 && c1 < c2);
+}
+
+// This lane's ray a against the ray b of lanes (g + r) % W of its W-lane group,
+// r = r_begin .. r_end.  Every lane of the wave calls it (shuffles).
+template <int W>
+__device__ __forceinline__ void pair_rounds(int g, const double (&a)[3], bool a_ok, const double (&b)[3], bool b_ok,
+                                            int r_begin, int r_end, Widest& best) {
+#pragma unroll 2
+    for (int r = r_begin; r <= r_end; ++r) {
+        const int src = (g + r) & (W - 1);
+        const double b0 = __shfl(b[0], src, W), b1 = __shfl(b[1], src, W), b2 = __shfl(b[2], src, W);
+        const int ok = __shfl((int)b_ok, src, W);
+        if (a_ok && ok) {
+            double c0, c1, c2;
+            {
+                // no contraction: the cross product of a ray with itself (two
+                // observations in one image) is exactly zero
+#pragma clang fp contract(off)
+                c0 = a[1] * b2 - a[2] * b1;
+                c1 = a[2] * b0 - a[0] * b2;
+                c2 = a[0] * b1 - a[1] * b0;
+            }
+            const double sn = sqrt(c0 * c0 + c1 * c1 + c2 * c2);
+            const double cs = a[0] * b0 + a[1] * b1 + a[2] * b2;
+            if (wider(sn, cs, best.s, best.c)) best = Widest{sn, cs};
+        }
+    }
+}
+
+// the widest pair of a W-lane group, in every lane of it
+template <int W>
+__device__ __forceinline__ void group_widest(Widest& best) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+        const double os = __shfl_xor(best.s, o, W), oc = __shfl_xor(best.c, o, W);
+        if (wider(os, oc, best.s, best.c)) best = Widest{os, oc};
+    }
+}
+
+__device__ __forceinline__ double widest_deg(const Widest& w) {
+    return atan2(w.s, w.c) * (180.0 / 3.14159265358979323846);
+}
+
+struct PointRule {
+    double min_angle_deg;
+    int32_t min_track;
+};
+// 0 kept, 1 short, 2 angle
+__device__ __forceinline__ int point_verdict(const PointRule& R, int survivors, double deg) {
+    if (survivors < R.min_track) return 1;
+    if (R.min_angle_deg > 0.0 && deg < R.min_angle_deg) return 2;
+    return 0;
+}
+
+__global__ __launch_bounds__(kPtThreads) void wash_point_kernel(WashInput in, PointRule R,
+                                                                const uint8_t* __restrict__ code,
+                                                                const double* __restrict__ ray,
+                                                                double* __restrict__ max_angle,
+                                                                uint8_t* __restrict__ keep_obs,
+                                                                uint8_t* __restrict__ keep_pt,
+                                                                unsigned long long* __restrict__ counts) {
+    __shared__ unsigned cnt[4];   // short, angle, points kept, observations kept
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 4) cnt[tid] = 0;
+    __syncthreads();
+    const int64_t kw = ((int64_t)blockIdx.x * (kPtThreads / 64) + wave) * kPtPerWave;   // the wave's first point
+    unsigned c[4] = {0, 0, 0, 0};
+    {
+        const int grp = lane / kWashGroup, g = lane % kWashGroup;
+        const int64_t k = kw + grp;
+        const bool has = k < in.n_pt;
+        const int32_t o0 = has ? in.pt_off[k] : 0;
+        const int32_t n = has ? in.pt_off[k + 1] - o0 : 0;
+        if (!__any(n > kWashGroup)) {
+            // ---- a lane group per point ----
+            const bool mine = g < n;
+            const int64_t s = (int64_t)o0 + g;
+            const bool ok = mine && code[s] == kWashKeep;
+            double a[3] = {0.0, 0.0, 0.0};
+            if (ok) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) a[j] = ray[3 * s + j];
+            }
+            Widest best{0.0, 1.0};
+            pair_rounds<kWashGroup>(g, a, ok, a, ok, 1, kWashGroup / 2, best);
+            group_widest<kWashGroup>(best);
+            const unsigned long long m = __ballot(ok);
+            const int survivors = __popcll((m >> (grp * kWashGroup)) & ((1ull << kWashGroup) - 1));
+            const double deg = widest_deg(best);
+            const int v = point_verdict(R, survivors, deg);
+            if (has && g == 0) {
+                const int64_t pm = in.pt_map ? in.pt_map[k] : k;
+                max_angle[pm] = deg;
+                keep_pt[pm] = v == 0;
+                c[0] += v == 1; c[1] += v == 2; c[2] += v == 0;
+            }
+            if (mine) {
+                const int64_t so = in.obs_map ? in.obs_map[s] : s;
+                const bool ko = v == 0 && ok;
+                keep_obs[so] = ko;
+                c[3] += ko;
+            }
+        } else {
+            // ---- a wave per point, pairs in rounds of 64 ----
+            for (int q = 0; q < kPtPerWave; ++q) {
+                const int64_t kq = kw + q;
+                if (kq >= in.n_pt) break;   // (wave-uniform)
+                const int32_t q0 = in.pt_off[kq];
+                const int32_t nq = in.pt_off[kq + 1] - q0;
+                const int nt = (nq + 63) / 64;
+                Widest best{0.0, 1.0};
+                int survivors = 0;
+                for (int ti = 0; ti < nt; ++ti) {
+                    const int i = ti * 64 + lane;
+                    const bool a_ok = i < nq && code[(int64_t)q0 + i] == kWashKeep;
+                    double a[3] = {0.0, 0.0, 0.0};
+                    if (a_ok) {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) a[j] = ray[3 * ((int64_t)q0 + i) + j];
+                    }
+                    survivors += __popcll(__ballot(a_ok));
+                    pair_rounds<64>(lane, a, a_ok, a, a_ok, 1, 32, best);
+                    for (int tj = ti + 1; tj < nt; ++tj) {
+                        const int jn = tj * 64 + lane;
+                        const bool b_ok = jn < nq && code[(int64_t)q0 + jn] == kWashKeep;
+                        double b[3] = {0.0, 0.0, 0.0};
+                        if (b_ok) {
+#pragma unroll
+                            for (int j = 0; j < 3; ++j) b[j] = ray[3 * ((int64_t)q0 + jn) + j];
+                        }
+                        pair_rounds<64>(lane, a, a_ok, b, b_ok, 0, 63, best);
+                    }
+                }
+                group_widest<64>(best);
+                const double deg = widest_deg(best);
+                const int v = point_verdict(R, survivors, deg);
+                if (lane == 0) {
+                    const int64_t pm = in.pt_map ? in.pt_map[kq] : kq;
+                    max_angle[pm] = deg;
+                    keep_pt[pm] = v == 0;
+                    c[0] += v == 1; c[1] += v == 2; c[2] += v == 0;
+                }
+                for (int i = lane; i < nq; i += 64) {
+                    const int64_t s = (int64_t)q0 + i;
+                    const int64_t so = in.obs_map ? in.obs_map[s] : s;
+                    const bool ko = v == 0 && code[s] == kWashKeep;
+                    keep_obs[so] = ko;
+                    c[3] += ko;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        unsigned v = c[t];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0 && v) atomicAdd(&cnt[t], v);
+    }
+    __syncthreads();
+    if (tid < 4 && cnt[tid]) {
+        const int slot[4] = {kWcPtShort, kWcPtAngle, kWcPtKept, kWcObsKept};
+        atomicAdd(&counts[slot[tid]], (unsigned long long)cnt[tid]);
+    }
+}
+
+}  // namespace
+
+void WashBuffers::alloc(int64_t n_pt_, int64_t n_obs_) {
+    n_pt = n_pt_;
+    n_obs = n_obs_;
+    residual.alloc(2 * (size_t)n_obs);
+    max_angle.alloc((size_t)n_pt);
+    keep_obs.alloc((size_t)n_obs);
+    keep_pt.alloc((size_t)n_pt);
+    code.alloc((size_t)n_obs);
+    ray.alloc(3 * (size_t)n_obs);
+    blk_pt.alloc(((size_t)n_obs + kObsThreads - 1) / kObsThreads);
+    counts.alloc(kWcCount);
+}
+
+void ba_wash_eval(const WashInput& in, const sfm_ba_wash_opts& o, WashBuffers& b, hipStream_t s, hipEvent_t* ev,
+                  double* ms) {
+    SFM_REQUIRE(b.n_pt == in.n_pt && b.n_obs == in.n_obs, SFM_ERR_INVALID_ARG, "internal: wash buffers of another size");
+    b.counts.zero(s);
+    const bool timed = ev && ms;
+    auto lap = [&](double* out) {
+        SFM_HIP(hipEventRecord(ev[1], s));
+        SFM_HIP(hipEventSynchronize(ev[1]));
+        float t = 0.f;
+        SFM_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
+        *out = t;
+    };
+    if (timed) {
+        ms[0] = ms[1] = 0.0;
+        SFM_HIP(hipEventRecord(ev[0], s));
+    }
+    if (in.n_obs > 0) {
+        hipLaunchKernelGGL(wash_block_point_kernel, dim3((unsigned)((in.n_pt + 255) / 256)), dim3(256), 0, s, in.pt_off,
+                           in.n_pt, b.blk_pt.p);
+        SFM_HIP(hipGetLastError());
+        const unsigned grid = (unsigned)(((int64_t)in.n_obs + kObsThreads - 1) / kObsThreads);
+        SFM_BY_MODEL_ALL(in, hipLaunchKernelGGL(wash_obs_kernel<CM>, dim3(grid), dim3(kObsThreads), 0, s, in,
+                                                o.max_residual_px, (int)o.cheirality, b.blk_pt.p,
+                                                reinterpret_cast<double2*>(b.residual.p), b.code.p, b.ray.p,
+                                                b.counts.p));
+        SFM_HIP(hipGetLastError());
+    }
+    if (timed) {
+        lap(&ms[0]);
+        SFM_HIP(hipEventRecord(ev[0], s));
+    }
+    if (in.n_pt > 0) {
+        const int per_block = (kPtThreads / 64) * kPtPerWave;
+        const unsigned grid = (unsigned)(((int64_t)in.n_pt + per_block - 1) / per_block);
+        hipLaunchKernelGGL(wash_point_kernel, dim3(grid), dim3(kPtThreads), 0, s, in,
+                           PointRule{o.min_angle_deg, o.min_track_len}, b.code.p, b.ray.p, b.max_angle.p, b.keep_obs.p,
+                           b.keep_pt.p, b.counts.p);
+        SFM_HIP(hipGetLastError());
+    }
+    if (timed) lap(&ms[1]);
+}
+
+void ba_wash_download(WashBuffers& b, double* residual, double* max_angle, uint8_t* keep_obs, uint8_t* keep_pt,
+                      sfm_ba_wash_stats* stats, hipStream_t s) {
+    const size_t no = (size_t)b.n_obs, np = (size_t)b.n_pt;
+    if (residual && no) SFM_HIP(hipMemcpyAsync(residual, b.residual.p, 2 * no * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (max_angle && np) SFM_HIP(hipMemcpyAsync(max_angle, b.max_angle.p, np * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (keep_obs && no) SFM_HIP(hipMemcpyAsync(keep_obs, b.keep_obs.p, no, hipMemcpyDeviceToHost, s));
+    if (keep_pt && np) SFM_HIP(hipMemcpyAsync(keep_pt, b.keep_pt.p, np, hipMemcpyDeviceToHost, s));
+    unsigned long long c[kWcCount] = {0};
+    if (stats) SFM_HIP(hipMemcpyAsync(c, b.counts.p, sizeof c, hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipStreamSynchronize(s));
+    if (stats) {
+        stats->n_obs_depth = (int64_t)c[kWcObsDepth];
+        stats->n_obs_residual = (int64_t)c[kWcObsResidual];
+        stats->n_pt_short = (int64_t)c[kWcPtShort];
+        stats->n_pt_angle = (int64_t)c[kWcPtAngle];
+        stats->n_obs_kept = (int64_t)c[kWcObsKept];
+        stats->n_pt_kept = (int64_t)c[kWcPtKept];
+    }
+}
+
+}  // namespace sfm

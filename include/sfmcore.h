@@ -698,6 +698,83 @@ typedef struct sfm_sparse_filter_stats {
 int sfm_sparse_filter(sfm_ctx* ctx, const char* matches_dir, const sfm_fmatrix_opts* opts,
                       sfm_sparse_filter_stats* stats);
 
+/* ------------------------------------------------------------------------ */
+/* Post-BA outlier rejection ("wash")                                        */
+/* The step BundleAdjuster::operator() left as a hook between the solve and  */
+/* updateWorld() (src/adjuster/BundleAdjuster.h:179-184, washPoint()), and    */
+/* the filter OpenMVG's engine runs after every BA (badTrackRejector(4.0):   */
+/* RemoveOutliers_PixelResidualError(4.0 px, min track length 2), then       */
+/* RemoveOutliers_AngleError(2.0 deg)); restated, parity unpinned            */
+/* (DESIGN.md §3).                                                           */
+/*                                                                          */
+/* Observation o of point p in image i: P = R(w_i) X_p + t_i, r = the        */
+/* unweighted residual of the problem's camera_model (what the solver        */
+/* squares before the loss).  It is rejected by the first rule that applies: */
+/*   depth     r is not finite, or cheirality != 0 and the point is not in   */
+/*             front of the camera (P[2] > 0; SFM_CAM_SNAVELY looks down -z: */
+/*             P[2] < 0)                                                     */
+/*   residual  max_residual_px > 0 and |r| > max_residual_px                 */
+/* Point p: over its surviving observations the rays d = R_i' P (camera      */
+/* centre to point, world axes); max_angle_deg = the largest angle between   */
+/* two of them, atan2(|a x b|, a.b) in degrees (0 with fewer than two; two   */
+/* observations in one image give 0).  OpenMVG takes the back-projected      */
+/* pixel bearing instead, which differs by the surviving residual only.  The */
+/* point is removed by the first rule that applies:                          */
+/*   short     survivors < min_track_len                                     */
+/*   angle     min_angle_deg > 0 and max_angle_deg < min_angle_deg           */
+/* and every observation of a removed point gets keep_obs = 0.               */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_ba_wash_opts {
+    double max_residual_px;   /* 4.0; <= 0: no residual rule                   */
+    double min_angle_deg;     /* 2.0; <= 0: no angle rule                      */
+    int32_t min_track_len;    /* 2 (>= 1)                                      */
+    int32_t cheirality;       /* 1                                             */
+} sfm_ba_wash_opts;
+typedef struct sfm_ba_wash_stats {
+    int64_t n_obs_depth, n_obs_residual;   /* rejected observations, by rule   */
+    int64_t n_pt_short, n_pt_angle;        /* removed points, by rule          */
+    int64_t n_obs_kept, n_pt_kept;
+} sfm_ba_wash_stats;
+/* [cpu] {4.0, 2.0, 2, 1}; NULL opts below select them. */
+void sfm_ba_wash_default_options(sfm_ba_wash_opts* opts);
+
+/* One-shot: uploads the problem and the parameters, evaluates, downloads.
+ * Outputs are in the problem's own observation / point order; any of them may
+ * be NULL.  It does not shard: on a world_size > 1 context every rank
+ * evaluates the whole problem.  Argument checks as sfm_ba_plan_create's, and
+ * min_track_len >= 1 (SFM_ERR_INVALID_ARG). */
+int sfm_ba_wash(sfm_ctx* ctx, const sfm_ba_problem* prob, const double* extr, const double* intr,
+                const double* X, const sfm_ba_wash_opts* opts, double* residual /* [2*n_obs] */,
+                double* max_angle_deg /* [n_pt] */, uint8_t* keep_obs /* [n_obs] */,
+                uint8_t* keep_pt /* [n_pt] */, sfm_ba_wash_stats* stats);
+
+/* Resident: at the plan's current parameters (what sfm_ba_plan_download
+ * returns; before the first run, the parameters the plan was created with) on
+ * the observations already in HBM: nothing observation-sized is uploaded.
+ * The same outputs, bit for bit, as sfm_ba_wash at those parameters.  What it
+ * needs beyond the plan's arrays (the map from the plan's sorted layout to
+ * the problem's order, scratch) is built by the first call and kept.  A plan
+ * of a world_size > 1 context returns SFM_ERR_UNSUPPORTED (a shard holds only
+ * its own points). */
+int sfm_ba_plan_wash(sfm_ba_plan* plan, const sfm_ba_wash_opts* opts, double* residual,
+                     double* max_angle_deg, uint8_t* keep_obs, uint8_t* keep_pt,
+                     sfm_ba_wash_stats* stats);
+/* Device time (HIP events) of the two kernels of the plan's last
+ * sfm_ba_plan_wash: the observation pass and the point pass.  Only a plan of
+ * a context created with SFM_CTX_TIME_KERNELS times them; -1 otherwise. */
+int sfm_ba_plan_wash_last_ms(sfm_ba_plan* plan, double* obs_ms, double* point_ms);
+
+/* [cpu] The washed problem: the kept points in their old order, each with its
+ * kept observations in their old order; images, intrinsics, const_img and the
+ * model are untouched (the planner takes unobserved images).  pt_map[k] = the
+ * old index of new point k.  The output arrays are sized from the wash's
+ * stats: pt_offsets[n_pt_kept + 1], obs_img[n_obs_kept], obs_uv[2*n_obs_kept],
+ * X_out[3*n_pt_kept], pt_map[n_pt_kept]; any may be NULL.  A kept observation
+ * of a removed point is SFM_ERR_INVALID_ARG. */
+int sfm_ba_wash_apply(const sfm_ba_problem* prob, const double* X, const uint8_t* keep_obs,
+                      const uint8_t* keep_pt, int64_t* pt_offsets, int32_t* obs_img, double* obs_uv,
+                      double* X_out, int64_t* pt_map);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
