@@ -52,6 +52,9 @@ def SFM_CTX_BA_REDUCE_WAVES(n):
 
 SFM_RCS_BCR, SFM_RCS_DENSE, SFM_RCS_SEQ_BAND = 0, 1, 2
 
+SFM_TRI_LINEAR, SFM_TRI_ROBUST = 0, 1
+SFM_TRI_OK, SFM_TRI_SHORT, SFM_TRI_ANGLE, SFM_TRI_INFINITE = 0, 1, 2, 3
+
 SFM_MATCH_RATIO = 0
 SFM_MATCH_MUTUAL = 1
 SFM_MATCH_CASCADE = 2
@@ -139,6 +142,18 @@ class BAWashStats(C.Structure):
     _fields_ = [("n_obs_depth", C.c_int64), ("n_obs_residual", C.c_int64),
                 ("n_pt_short", C.c_int64), ("n_pt_angle", C.c_int64),
                 ("n_obs_kept", C.c_int64), ("n_pt_kept", C.c_int64)]
+
+
+class TriOpts(C.Structure):
+    _fields_ = [("method", C.c_int32), ("max_hypotheses", C.c_int32),
+                ("max_residual_px", C.c_double), ("min_angle_deg", C.c_double),
+                ("min_track_len", C.c_int32), ("cheirality", C.c_int32)]
+
+
+class TriStats(C.Structure):
+    _fields_ = [("n_pt_ok", C.c_int64), ("n_pt_short", C.c_int64), ("n_pt_angle", C.c_int64),
+                ("n_pt_infinite", C.c_int64), ("n_obs_kept", C.c_int64), ("n_obs_bad", C.c_int64),
+                ("n_obs_depth", C.c_int64), ("n_obs_residual", C.c_int64)]
 
 
 class SynthBAConfig(C.Structure):
@@ -260,6 +275,11 @@ SIGNATURES = [
                                    C.POINTER(BAWashStats)]),
     ("sfm_ba_plan_wash_last_ms", C.c_int, [C.c_void_p, f64p, f64p]),
     ("sfm_ba_wash_apply", C.c_int, [C.POINTER(BAProblem), f64p, u8p, u8p, i64p, i32p, f64p, f64p, i64p]),
+    ("sfm_tri_default_options", None, [C.POINTER(TriOpts)]),
+    ("sfm_triangulate", C.c_int, [C.c_void_p, C.POINTER(BAProblem), f64p, f64p, C.POINTER(TriOpts),
+                                  f64p, u8p, u8p, f64p, C.POINTER(TriStats)]),
+    ("sfm_triangulate_host", C.c_int, [C.POINTER(BAProblem), f64p, f64p, C.POINTER(TriOpts),
+                                       f64p, u8p, u8p, f64p, C.POINTER(TriStats)]),
     ("sfm_ba_intr_width", C.c_int, [C.c_int32]),
     ("sfm_ba_partition", C.c_int, [C.POINTER(BAProblem), C.c_int32, i64p, i64p]),
     ("sfm_ba_describe", C.c_int, [C.POINTER(BAProblem), C.c_int32, C.c_int32, C.POINTER(BAPlanShape)]),

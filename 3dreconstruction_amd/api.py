@@ -422,6 +422,36 @@ def ba_wash_apply(problem, X, keep_obs, keep_pt):
     return pr, Xo[:3 * n_pt], pm[:n_pt]
 
 
+def tri_default_options():
+    o = abi.TriOpts()
+    abi.load().sfm_tri_default_options(C.byref(o))
+    return o
+
+
+def triangulate(ctx, problem, extr, intr, opts=None):
+    """sfm_triangulate (ctx None: sfm_triangulate_host, on the CPU): every point
+    of `problem` from its track and the cameras (extr, intr).  dict(X [n_pt, 3]
+    (NaN where the point is not OK), status [n_pt] (SFM_TRI_*), keep_obs [n_obs]
+    (bool), residual [n_obs, 2], stats), in the problem's own order.  opts:
+    TriOpts (None: the defaults, tri_default_options())."""
+    n_pt, n_obs = problem.n_pt, problem.n_obs
+    X = np.zeros(3 * max(n_pt, 1))
+    st = np.zeros(max(n_pt, 1), np.uint8)
+    ko = np.zeros(max(n_obs, 1), np.uint8)
+    r = np.zeros(2 * max(n_obs, 1))
+    stats = abi.TriStats()
+    args = (C.byref(problem), abi.ptr(extr, abi.f64p), abi.ptr(intr, abi.f64p),
+            C.byref(opts) if opts is not None else None, abi.ptr(X, abi.f64p), abi.ptr(st, abi.u8p),
+            abi.ptr(ko, abi.u8p), abi.ptr(r, abi.f64p), C.byref(stats))
+    if ctx is None:
+        _check(abi.load().sfm_triangulate_host(*args), "sfm_triangulate_host")
+    else:
+        _check(ctx.lib.sfm_triangulate(ctx.h, *args), "sfm_triangulate")
+    return dict(X=X[:3 * n_pt].reshape(-1, 3), status=st[:n_pt], keep_obs=ko[:n_obs].astype(bool),
+                residual=r[:2 * n_obs].reshape(-1, 2),
+                stats={f: getattr(stats, f) for f, _ in abi.TriStats._fields_})
+
+
 def ba_cache_stats(ctx):
     """(reused, grown, fresh) plan counts of sfm_ba_solve on this context."""
     r, g, f = C.c_int64(), C.c_int64(), C.c_int64()

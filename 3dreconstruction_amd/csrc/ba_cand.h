@@ -13,8 +13,9 @@ namespace {
 
 constexpr double kCandEps = 2.220446049250313e-16;  // std::numeric_limits<double>::epsilon()
 
-// Rodrigues terms of one camera (extrinsics e = [w | t])
-__device__ inline CamPre make_campre(const double* e) {
+// Rodrigues terms of one camera (extrinsics e = [w | t]); also built on the
+// host by sfm_triangulate_host (tri.cpp)
+__host__ __device__ inline CamPre make_campre(const double* e) {
     CamPre cp;
     const double w[3] = {e[0], e[1], e[2]};
     const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];

@@ -4,6 +4,8 @@
 //   Matcher               cv::BFMatcher(NORM_L2, crossCheck=true) as created by
 //                         SequentialActuator.h:77 (exact mutual nearest neighbour)
 //   LocalFrame/GlobalFrame src/frame/LocalFrame.h:19-83, GlobalFrame.h:15-160
+//   Triangulator          every world point from its track and the current
+//                         poses (triangulator.hpp; sfm_triangulate)
 //   sparse::sparseBuilder src/sparseBuilder/sparseBuilder.h:14-39 — matchPair()
 //                         (exhaustive pairs, .cpp:758-807) and match()
 //                         (Matcher_Regions(0.8, BRUTE_FORCE_L2), .cpp:809-1023)
@@ -28,6 +30,7 @@
 #include "actuator.hpp"
 #include "adjuster.hpp"
 #include "frames.hpp"
+#include "triangulator.hpp"
 #include "world.hpp"
 
 namespace sfm {
@@ -116,6 +119,24 @@ class BundleAdjuster : public BasicBundleAdjuster<GpuSolver> {
    public:
     explicit BundleAdjuster(Context& ctx = Context::thread_default(), Options opt = Options())
         : BasicBundleAdjuster<GpuSolver>(GpuSolver{&ctx}, opt) {}
+};
+
+// ---------------------------------------------------------------------------
+// Triangulator (triangulator.hpp) on the GPU: sfm_triangulate
+// ---------------------------------------------------------------------------
+struct GpuTriBackend {
+    Context* ctx;
+    int triangulate(const sfm_ba_problem& pr, const double* extr, const double* intr, const sfm_tri_opts& o, double* X,
+                    uint8_t* status, uint8_t* keep_obs, sfm_tri_stats& st) const {
+        return sfm_triangulate(ctx->get(), &pr, extr, intr, &o, X, status, keep_obs, nullptr, &st);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+class Triangulator : public BasicTriangulator<GpuTriBackend> {
+   public:
+    explicit Triangulator(Context& ctx = Context::thread_default())
+        : BasicTriangulator<GpuTriBackend>(GpuTriBackend{&ctx}) {}
 };
 
 // ---------------------------------------------------------------------------

@@ -10,7 +10,8 @@ SRCS := $(wildcard $(CSRC)/*.cpp $(CSRC)/*.hip)
 OBJS := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/*.hpp)
 
-all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test
+all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
+     tests/cpp/triangulate_host_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -44,3 +45,12 @@ tests/cpp/facade_test: tests/cpp/facade_test.cpp 3dreconstruction_amd/include/sf
 tests/cpp/plan_pool_test: tests/cpp/plan_pool_test.cpp $(CSRC)/ba_plan.cpp $(HDRS)
 	g++ -O2 -std=c++17 -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< -L/opt/rocm/lib -lamdhip64 -lpthread \
 	    -Wl,-rpath,/opt/rocm/lib
+
+# sfm::Triangulator façade test (links the product), and the same file with
+# csrc/tri.cpp's host path compiled in (no library, no HIP runtime: host only)
+tests/cpp/triangulate_test: tests/cpp/triangulate_test.cpp $(wildcard $(PKG)/include/sfm/*.hpp) $(LIB)
+	g++ -O2 -std=c++17 -Wall -o $@ $< -I/opt/rocm/include -L3dreconstruction_amd/lib -lsfmcore \
+	    -Wl,-rpath,'$$ORIGIN/../../3dreconstruction_amd/lib'
+
+tests/cpp/triangulate_host_test: tests/cpp/triangulate_test.cpp $(CSRC)/tri.cpp $(HDRS)
+	g++ -O2 -std=c++17 -w -DTRI_STANDALONE -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $<

@@ -95,9 +95,9 @@ typedef struct sfm_ctx_opts {
  * every rank of a sharded solve then returns SFM_ERR_DEVICE together instead
  * of the others waiting in the next collective. */
 #define SFM_CTX_DIAG_FAIL_SOLVE_WAIT 4
-/* Measurement: sfm_fmatrix_ac brackets its kernel with HIP events (after
- * draining its uploads) so that sfm_ctx_last_kernel_ms can report the kernel
- * alone.  Off by default: the extra stream synchronisation and event pair are
+/* Measurement: sfm_fmatrix_ac and sfm_triangulate bracket their kernels with
+ * HIP events (after draining the uploads) so that sfm_ctx_last_kernel_ms can
+ * report the kernels alone.  Off by default: the extra stream synchronisation and event pair are
  * not part of the filter's production path. */
 #define SFM_CTX_TIME_KERNELS 8
 /* Diagnostic only (tests): the device's copy of the LM accept decision is
@@ -682,9 +682,9 @@ int sfm_fmatrix_ac(sfm_ctx* ctx, int64_t n_pairs, const int64_t* off, const doub
                    const int32_t* wh, const sfm_fmatrix_opts* opts,
                    sfm_fmatrix_result* results, int32_t* inliers);
 
-/* Device time (HIP events on the context's stream) of the kernel of the
- * context's last sfm_fmatrix_ac call, without its host normalisation,
- * uploads and downloads (measurement; no reference counterpart).  Only a
+/* Device time (HIP events on the context's stream) of the kernel(s) of the
+ * context's last sfm_fmatrix_ac or sfm_triangulate call, without its host
+ * normalisation, uploads and downloads (measurement; no reference counterpart).  Only a
  * context created with SFM_CTX_TIME_KERNELS times it; -1 otherwise. */
 int sfm_ctx_last_kernel_ms(sfm_ctx* ctx, double* ms);
 
@@ -774,6 +774,95 @@ int sfm_ba_plan_wash_last_ms(sfm_ba_plan* plan, double* obs_ms, double* point_ms
 int sfm_ba_wash_apply(const sfm_ba_problem* prob, const double* X, const uint8_t* keep_obs,
                       const uint8_t* keep_pt, int64_t* pt_offsets, int32_t* obs_img, double* obs_uv,
                       double* X_out, int64_t* pt_map);
+
+/* ------------------------------------------------------------------------ */
+/* Track triangulation                                                       */
+/* Points from known poses and tracks: OpenMVG's                             */
+/* ComputeStructureFromKnownPoses, and what its incremental engine does for  */
+/* new tracks after each resection (the reference triangulates two views at  */
+/* SequentialActuator.h:206-223).  The N-view solve is OpenMVG's             */
+/* TriangulateNViewAlgebraic; restated from its published code, parity       */
+/* unpinned.  ROBUST deliberately replaces OpenMVG's random   */
+/* minimal samples by an exhaustive (or, past max_hypotheses, evenly spread) */
+/* set of view pairs: every decision is a deterministic function of the      */
+/* input.                                                                    */
+/*                                                                          */
+/* The input is a sfm_ba_problem (const_img and huber_a are ignored) and the */
+/* cameras.  Per point, over its observations in order:                      */
+/*   bearing   PINHOLE b = ((u-cx)/fx, (v-cy)/fy, 1); RADIAL3 p_d =          */
+/*             ((u-ppx)/f, (v-ppy)/f), undistorted by exactly 20 iterations  */
+/*             p_u <- p_d / c(|p_u|^2) from p_u = p_d, b = (p_u, 1); SNAVELY */
+/*             p_d = (u/f, v/f), the same iteration with d(), b = (p_u, -1). */
+/*             b is normalised; an observation whose b is not finite is bad: */
+/*             it takes no part in any solve (n_obs_bad).                    */
+/*   solve     over a set of observations: M = sum C'C, C = (I - b b')[R|t], */
+/*             summed in observation order; v = the eigenvector of M's       */
+/*             smallest eigenvalue (cyclic Jacobi, at most 30 sweeps),       */
+/*             X = v[0..2] / v[3]; INFINITE unless |v[3]| > 1e-12 and X is   */
+/*             finite.                                                       */
+/*   judge     an observation at X, by sfm_ba_wash's rules: depth (residual  */
+/*             not finite, or cheirality and not in front), else residual    */
+/*             (max_residual_px > 0 and |r| > max_residual_px).              */
+/*   LINEAR    one solve over every good observation; keep_obs = those that  */
+/*             pass the judgement at X (no refit).                           */
+/*   ROBUST    hypotheses = the pairs (a, b), a < b, of good observations of */
+/*             different images, in lexicographic order; when there are more */
+/*             than max_hypotheses, pair floor(h * npairs / max_hypotheses)  */
+/*             for h = 0 .. max_hypotheses-1.  Each is solved from its two   */
+/*             views and judged on every good observation; the best has the  */
+/*             most inliers, then the smallest sum of squared inlier         */
+/*             residuals, then the lowest h (an INFINITE hypothesis has no   */
+/*             inliers).  One solve over the winner's inliers, and one       */
+/*             judgement of every observation at that X: keep_obs.           */
+/* Point status, the first that applies:                                     */
+/*   SHORT     fewer than two good observations, no hypothesis, a ROBUST     */
+/*             winner with fewer than two inliers (nothing to solve from);   */
+/*   INFINITE  the final solve;                                              */
+/*   SHORT     fewer than min_track_len kept observations;                   */
+/*   ANGLE     min_angle_deg > 0 and the largest angle between two kept      */
+/*             observations' measured rays R' b, atan2(|a x b|, a.b), is     */
+/*             below it (exactly 0 for two observations of one image).       */
+/* A point that is not OK gets X = NaN and keep_obs = 0 throughout.          */
+/* residual is the residual at the final X of the solve (also when the point */
+/* was then removed as SHORT or ANGLE); NaN where there is no such X and at  */
+/* bad observations.  n_obs_depth / n_obs_residual count the final           */
+/* judgement's rejections.                                                   */
+/* ------------------------------------------------------------------------ */
+#define SFM_TRI_LINEAR 0   /* every observation, one N-view algebraic solve      */
+#define SFM_TRI_ROBUST 1   /* two-view hypotheses, consensus, N-view refit        */
+#define SFM_TRI_OK       0
+#define SFM_TRI_SHORT    1
+#define SFM_TRI_ANGLE    2
+#define SFM_TRI_INFINITE 3
+typedef struct sfm_tri_opts {
+    int32_t method;           /* SFM_TRI_ROBUST                                   */
+    int32_t max_hypotheses;   /* 64 (>= 1): ROBUST hypotheses per point           */
+    double  max_residual_px;  /* 4.0; <= 0: no residual rule                      */
+    double  min_angle_deg;    /* 2.0; <= 0: no angle rule                         */
+    int32_t min_track_len;    /* 2 (>= 2)                                         */
+    int32_t cheirality;       /* 1                                                */
+} sfm_tri_opts;
+typedef struct sfm_tri_stats {
+    int64_t n_pt_ok, n_pt_short, n_pt_angle, n_pt_infinite;
+    int64_t n_obs_kept, n_obs_bad, n_obs_depth, n_obs_residual;
+} sfm_tri_stats;
+/* [cpu] {ROBUST, 64, 4.0, 2.0, 2, 1}; NULL opts below select them. */
+void sfm_tri_default_options(sfm_tri_opts* opts);
+/* One-shot: uploads the problem and the cameras, triangulates every point,
+ * downloads.  Outputs are in the problem's own order; any may be NULL.
+ * Argument checks as sfm_ba_wash's, method, min_track_len >= 2 and
+ * max_hypotheses >= 1 (SFM_ERR_INVALID_ARG).  It does not shard: on a
+ * world_size > 1 context every rank triangulates the whole problem.  A
+ * context created with SFM_CTX_TIME_KERNELS reports the kernels' device time
+ * through sfm_ctx_last_kernel_ms. */
+int sfm_triangulate(sfm_ctx* ctx, const sfm_ba_problem* prob, const double* extr, const double* intr,
+                    const sfm_tri_opts* opts, double* X /* [3*n_pt] */, uint8_t* status /* [n_pt] */,
+                    uint8_t* keep_obs /* [n_obs] */, double* residual /* [2*n_obs] */, sfm_tri_stats* stats);
+/* [cpu] The same on the host, a serial loop over the same per-point code
+ * (results agree with the device's to rounding, not bit for bit). */
+int sfm_triangulate_host(const sfm_ba_problem* prob, const double* extr, const double* intr,
+                         const sfm_tri_opts* opts, double* X, uint8_t* status, uint8_t* keep_obs,
+                         double* residual, sfm_tri_stats* stats);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
