@@ -1,6 +1,6 @@
 // Device helpers shared by the bundle-adjustment kernels for CDNA4 (gfx950),
 // fp64 throughout: ba_gram.hip, ba_schur.hip, ba_reduce.hip, ba_step.hip
-// (and ba_wash.hip, which restates linearize()'s projection without Jacobians).
+// (and track.h, which restates linearize()'s projection without Jacobians).
 // (ba_bcr.hip keeps its own rsqrt_nr / clampd / stamp and does not include this.)
 //
 // Reference: src/adjuster/BundleAdjuster.h — ReprojectCost :33-69 (pinhole,

@@ -924,7 +924,7 @@ void wash_plan(sfm_ba_plan* pl, const sfm_ba_wash_opts& O) {
     const double* in = !ran ? pl->intr0.p : pl->cur_is_a ? pl->ia.p : pl->ib.p;
     const double* x = !ran ? pl->X0.p : pl->cur_is_a ? pl->Xa.p : pl->Xb.p;
     ba_campre(e, h.n_img, pl->wash_cp.p, s);
-    WashInput W;
+    TrackInput W;
     W.n_pt = (int32_t)h.n_spt; W.n_obs = (int32_t)h.n_sobs;
     W.cam_model = pl->P.cam_model; W.iw = h.iw;
     W.pt_off = pl->pt_off.p; W.obs_img = pl->obs_img.p; W.obs_uv = pl->obs_uv.p; W.img_intr = pl->img_intr.p;

@@ -1,5 +1,5 @@
 // Post-BA outlier rejection, host side: the options, the one-shot entry point
-// (sfm_ba_wash: caller-order arrays uploaded as they are, identity maps) and
+// (sfm_ba_wash: a TrackUpload of the caller-order arrays, identity maps) and
 // the compaction of a problem by the masks a wash returned (sfm_ba_wash_apply,
 // host only).  The resident entry point, sfm_ba_plan_wash, is in ba_solver.cpp
 // next to the plan it reads; both run the kernels of ba_wash.hip.
@@ -40,30 +40,11 @@ extern "C" int sfm_ba_wash(sfm_ctx* ctx, const sfm_ba_problem* prob, const doubl
         validate_problem(*prob);
         CtxScope scope_(ctx);
         hipStream_t s = ctx->stream;
-        const int iw = sfm_ba_intr_width(prob->camera_model);
-        const size_t np = (size_t)prob->n_pt, no = (size_t)prob->n_obs;
-        HostVec<int32_t> off(np + 1);
-        for (size_t p = 0; p <= np; ++p) off[p] = (int32_t)prob->pt_offsets[p];
-        DBuf<int32_t> d_off, d_img, d_img_intr;
-        DBuf<double> d_uv, d_extr, d_intr, d_X;
-        DBuf<CamPre> d_cp;
-        d_off.alloc(np + 1); d_off.upload(off.data(), np + 1, s);
-        d_img.alloc(no); d_img.upload(prob->obs_img, no, s);
-        d_uv.alloc(2 * no); d_uv.upload(prob->obs_uv, 2 * no, s);
-        d_img_intr.alloc(prob->n_img); d_img_intr.upload(prob->img_intr, prob->n_img, s);
-        d_extr.alloc(6 * (size_t)prob->n_img); d_extr.upload(extr, 6 * (size_t)prob->n_img, s);
-        d_intr.alloc((size_t)iw * prob->n_intr); d_intr.upload(intr, (size_t)iw * prob->n_intr, s);
-        d_X.alloc(3 * np); d_X.upload(X, 3 * np, s);
-        d_cp.alloc(prob->n_img);
-        ba_campre(d_extr.p, prob->n_img, d_cp.p, s);
-        WashInput in;
-        in.n_pt = (int32_t)np; in.n_obs = (int32_t)no;
-        in.cam_model = prob->camera_model; in.iw = iw;
-        in.pt_off = d_off.p; in.obs_img = d_img.p; in.obs_uv = d_uv.p; in.img_intr = d_img_intr.p;
-        in.cp = d_cp.p; in.intr = d_intr.p; in.X = d_X.p;
+        TrackUpload up(*prob, extr, intr, X, s);
+        ba_campre(up.extr.p, prob->n_img, up.cp.p, s);
         WashBuffers b;
         b.alloc(prob->n_pt, prob->n_obs);
-        ba_wash_eval(in, O, b, s);
+        ba_wash_eval(up.in, O, b, s);
         ba_wash_download(b, residual, max_angle_deg, keep_obs, keep_pt, stats, s);
         return SFM_OK;
     });

@@ -1,7 +1,8 @@
 // Post-BA outlier rejection ("wash"): per-observation residual
 // and depth test, per-point survivor count and largest angle between the
-// surviving rays (ba_wash.hip), behind sfm_ba_wash (ba_wash.cpp: caller-order
-// arrays, identity maps) and sfm_ba_plan_wash (ba_solver.cpp: the plan's shard
+// surviving rays (ba_wash.hip over the shared pieces of track.h), behind
+// sfm_ba_wash (ba_wash.cpp: a TrackUpload of the caller's arrays, identity
+// maps) and sfm_ba_plan_wash (ba_solver.cpp: a TrackInput over the plan's shard
 // arrays, results scattered through its shard -> problem maps).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,34 +11,12 @@
 
 #include "ba_types.h"
 #include "common.h"
+#include "track.h"
 
 namespace sfm {
 
-// reject code of an observation (obs pass -> point pass)
-enum : uint8_t { kWashKeep = 0, kWashDepth = 1, kWashResidual = 2 };
 // counters, in sfm_ba_wash_stats order
 enum : int { kWcObsDepth = 0, kWcObsResidual, kWcPtShort, kWcPtAngle, kWcObsKept, kWcPtKept, kWcCount };
-
-// lanes per point of the point pass's short form (a point of up to this many
-// observations shares its wave with 64 / kWashGroup - 1 others); longer
-// points take a whole wave each, in rounds of 64 observations
-constexpr int kWashGroup = 16;
-
-// What the two kernels read: observations grouped by point in "kernel order"
-// (the caller's, or a plan's shard order) and the parameters.
-struct WashInput {
-    int32_t n_pt = 0, n_obs = 0, cam_model = 0, iw = 4;
-    const int32_t* pt_off = nullptr;    // [n_pt + 1]
-    const int32_t* obs_img = nullptr;   // [n_obs]
-    const double* obs_uv = nullptr;     // [2 * n_obs]
-    const int32_t* img_intr = nullptr;  // [n_img]
-    const CamPre* cp = nullptr;         // [n_img]
-    const double* intr = nullptr;       // [iw * n_intr]
-    const double* X = nullptr;          // [3 * n_pt], kernel order
-    // kernel order -> caller order (null: the identity)
-    const int32_t* pt_map = nullptr;    // [n_pt]
-    const int32_t* obs_map = nullptr;   // [n_obs]
-};
 
 // Device results (caller order) and scratch (kernel order) of one evaluation;
 // a plan keeps them from its first wash on.
@@ -56,7 +35,7 @@ struct WashBuffers {
 
 // Both passes on stream s.  ev (two events) + ms[2]: the kernels' device
 // times (observation pass, point pass) when ms is given; it synchronises.
-void ba_wash_eval(const WashInput& in, const sfm_ba_wash_opts& o, WashBuffers& b, hipStream_t s,
+void ba_wash_eval(const TrackInput& in, const sfm_ba_wash_opts& o, WashBuffers& b, hipStream_t s,
                   hipEvent_t* ev = nullptr, double* ms = nullptr);
 // Results to the caller's arrays (each may be null); synchronises the stream.
 void ba_wash_download(WashBuffers& b, double* residual, double* max_angle, uint8_t* keep_obs, uint8_t* keep_pt,

@@ -3,32 +3,27 @@
 // RemoveOutliers_PixelResidualError, then RemoveOutliers_AngleError) and the
 // reference left as a hook (src/adjuster/BundleAdjuster.h:179-184, washPoint()).
 //
-//   obs pass    one lane per observation: P = R X + t, the unweighted residual of
-//               the problem's camera model (the solver's projection formulas),
-//               the depth / residual reject code and the ray R' P.  Streaming:
-//               reads image 4 B + measurement 16 B, writes residual 16 B + code
-//               1 B + ray 24 B per observation (the cameras and points it gathers
-//               are shared by neighbouring lanes).
-//   point pass  survivors, the short-track rule and the largest angle between two
-//               surviving rays, in one pass: a point of <= kWashGroup
-//               observations takes a lane group (64 / kWashGroup points per
-//               wave), a longer one a whole wave, all pairs in rounds of 64.
-//               The widest pair is chosen by comparing (|a x b|, a.b) tuples;
-//               one atan2 per point.
+//   obs pass    one lane per observation: project_residual and obs_verdict
+//               (track.h) at the point's X -- P = R X + t, the unweighted
+//               residual of the problem's camera model, the depth / residual
+//               reject code -- and the ray R' P.
+//               Streaming: reads image 4 B + measurement 16 B, writes residual
+//               16 B + code 1 B + ray 24 B per observation (the cameras and
+//               points it gathers are shared by neighbouring lanes).
+//   point pass  track_point_kernel (track.h) with the WashPoint policy below:
+//               survivors, the short-track rule and the largest angle between
+//               two surviving rays, in one pass.
 //
 // Both write their results through kernel-order -> caller-order maps (a plan's
 // shard order; null for arrays already in caller order).  The counters are
 // integer block sums added with integer atomics: the same numbers every run.
 #include "ba_wash.h"
-#include "ba_wash_device.h"
 
 namespace sfm {
 namespace {
 
 constexpr int kObsThreads = 256;
 constexpr int kWin = kObsThreads + 2;   // pt_off window of an observation block: its points and their end
-constexpr int kPtThreads = 256;
-constexpr int kPtPerWave = 64 / kWashGroup;
 
 // blk_pt[b] = the point owning observation b * kObsThreads (one lane per point)
 __global__ __launch_bounds__(256) void wash_block_point_kernel(const int32_t* __restrict__ pt_off, int32_t n_pt,
@@ -40,7 +35,7 @@ __global__ __launch_bounds__(256) void wash_block_point_kernel(const int32_t* __
 }
 
 template <int CM>
-__global__ __launch_bounds__(kObsThreads) void wash_obs_kernel(WashInput in, double max_res, int cheirality,
+__global__ __launch_bounds__(kObsThreads) void wash_obs_kernel(TrackInput in, ObsRule rule,
                                                                const int32_t* __restrict__ blk_pt,
                                                                double2* __restrict__ residual,
                                                                uint8_t* __restrict__ code, double* __restrict__ ray,
@@ -53,7 +48,7 @@ __global__ __launch_bounds__(kObsThreads) void wash_obs_kernel(WashInput in, dou
     for (int i = tid; i < kWin; i += kObsThreads) win[i] = in.pt_off[min((int64_t)p0 + i, (int64_t)in.n_pt)];
     if (tid < 2) cnt[tid] = 0;
     __syncthreads();
-    uint8_t cd = kWashKeep;
+    uint8_t cd = kObsKeep;
     const bool live = s < in.n_obs;
     if (live) {
         // the observation's point: the last one of the window starting at or before s
@@ -78,10 +73,8 @@ __global__ __launch_bounds__(kObsThreads) void wash_obs_kernel(WashInput in, dou
         const double X[3] = {Xp[0], Xp[1], Xp[2]};
         const double2 uv = reinterpret_cast<const double2*>(in.obs_uv)[s];
         double P[3], r0, r1;
-        wash_project<CM>(cp, ib, X, uv.x, uv.y, P, r0, r1);
-        const bool front = CM == SFM_CAM_SNAVELY ? P[2] < 0.0 : P[2] > 0.0;
-        if (!(isfinite(r0) && isfinite(r1)) || (cheirality != 0 && !front)) cd = kWashDepth;
-        else if (max_res > 0.0 && sqrt(r0 * r0 + r1 * r1) > max_res) cd = kWashResidual;
+        project_residual<CM>(cp, ib, X, uv.x, uv.y, P, r0, r1);
+        cd = obs_verdict<CM>(rule, P, r0, r1);
         const int64_t so = in.obs_map ? in.obs_map[s] : s;
         residual[so] = make_double2(r0, r1);
         code[s] = cd;
@@ -90,7 +83,7 @@ __global__ __launch_bounds__(kObsThreads) void wash_obs_kernel(WashInput in, dou
 #pragma unroll
         for (int j = 0; j < 3; ++j) d[j] = cp.R[j] * P[0] + cp.R[3 + j] * P[1] + cp.R[6 + j] * P[2];
     }
-    const unsigned long long md = __ballot(cd == kWashDepth), mr = __ballot(cd == kWashResidual);
+    const unsigned long long md = __ballot(cd == kObsDepth), mr = __ballot(cd == kObsResidual);
     if ((tid & 63) == 0) {
         if (md) atomicAdd(&cnt[0], (unsigned)__popcll(md));
         if (mr) atomicAdd(&cnt[1], (unsigned)__popcll(mr));
@@ -99,128 +92,30 @@ __global__ __launch_bounds__(kObsThreads) void wash_obs_kernel(WashInput in, dou
     if (tid < 2 && cnt[tid]) atomicAdd(&counts[tid == 0 ? kWcObsDepth : kWcObsResidual], (unsigned long long)cnt[tid]);
 }
 
-struct PointRule {
-    double min_angle_deg;
-    int32_t min_track;
+// The wash's side of the point pass (track.h): the verdict is the point rule
+// alone; max_angle, keep_pt and keep_obs go out through the maps.
+struct WashPoint {
+    static constexpr int kCounts = 4;   // short, angle, points kept, observations kept
+    __device__ static int slot(int t) {
+        const int s[kCounts] = {kWcPtShort, kWcPtAngle, kWcPtKept, kWcObsKept};
+        return s[t];
+    }
+    PointRule rule;
+    double* __restrict__ max_angle;
+    uint8_t* __restrict__ keep_obs;
+    uint8_t* __restrict__ keep_pt;
+    __device__ int verdict(int64_t, int survivors, double deg) const { return point_rule(rule, survivors, deg); }
+    __device__ void point(const TrackInput& in, int64_t k, int v, double deg, unsigned (&c)[kCounts]) const {
+        const int64_t pm = in.pt_map ? in.pt_map[k] : k;
+        max_angle[pm] = deg;
+        keep_pt[pm] = v == 0;
+        c[0] += v == 1; c[1] += v == 2; c[2] += v == 0;
+    }
+    __device__ void obs(const TrackInput& in, int64_t s, bool keep, unsigned (&c)[kCounts]) const {
+        keep_obs[in.obs_map ? in.obs_map[s] : s] = keep;
+        c[3] += keep;
+    }
 };
-// 0 kept, 1 short, 2 angle
-__device__ __forceinline__ int point_verdict(const PointRule& R, int survivors, double deg) {
-    if (survivors < R.min_track) return 1;
-    if (R.min_angle_deg > 0.0 && deg < R.min_angle_deg) return 2;
-    return 0;
-}
-
-__global__ __launch_bounds__(kPtThreads) void wash_point_kernel(WashInput in, PointRule R,
-                                                                const uint8_t* __restrict__ code,
-                                                                const double* __restrict__ ray,
-                                                                double* __restrict__ max_angle,
-                                                                uint8_t* __restrict__ keep_obs,
-                                                                uint8_t* __restrict__ keep_pt,
-                                                                unsigned long long* __restrict__ counts) {
-    __shared__ unsigned cnt[4];   // short, angle, points kept, observations kept
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 4) cnt[tid] = 0;
-    __syncthreads();
-    const int64_t kw = ((int64_t)blockIdx.x * (kPtThreads / 64) + wave) * kPtPerWave;   // the wave's first point
-    unsigned c[4] = {0, 0, 0, 0};
-    {
-        const int grp = lane / kWashGroup, g = lane % kWashGroup;
-        const int64_t k = kw + grp;
-        const bool has = k < in.n_pt;
-        const int32_t o0 = has ? in.pt_off[k] : 0;
-        const int32_t n = has ? in.pt_off[k + 1] - o0 : 0;
-        if (!__any(n > kWashGroup)) {
-            // ---- a lane group per point ----
-            const bool mine = g < n;
-            const int64_t s = (int64_t)o0 + g;
-            const bool ok = mine && code[s] == kWashKeep;
-            double a[3] = {0.0, 0.0, 0.0};
-            if (ok) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) a[j] = ray[3 * s + j];
-            }
-            Widest best{0.0, 1.0};
-            pair_rounds<kWashGroup>(g, a, ok, a, ok, 1, kWashGroup / 2, best);
-            group_widest<kWashGroup>(best);
-            const unsigned long long m = __ballot(ok);
-            const int survivors = __popcll((m >> (grp * kWashGroup)) & ((1ull << kWashGroup) - 1));
-            const double deg = widest_deg(best);
-            const int v = point_verdict(R, survivors, deg);
-            if (has && g == 0) {
-                const int64_t pm = in.pt_map ? in.pt_map[k] : k;
-                max_angle[pm] = deg;
-                keep_pt[pm] = v == 0;
-                c[0] += v == 1; c[1] += v == 2; c[2] += v == 0;
-            }
-            if (mine) {
-                const int64_t so = in.obs_map ? in.obs_map[s] : s;
-                const bool ko = v == 0 && ok;
-                keep_obs[so] = ko;
-                c[3] += ko;
-            }
-        } else {
-            // ---- a wave per point, pairs in rounds of 64 ----
-            for (int q = 0; q < kPtPerWave; ++q) {
-                const int64_t kq = kw + q;
-                if (kq >= in.n_pt) break;   // (wave-uniform)
-                const int32_t q0 = in.pt_off[kq];
-                const int32_t nq = in.pt_off[kq + 1] - q0;
-                const int nt = (nq + 63) / 64;
-                Widest best{0.0, 1.0};
-                int survivors = 0;
-                for (int ti = 0; ti < nt; ++ti) {
-                    const int i = ti * 64 + lane;
-                    const bool a_ok = i < nq && code[(int64_t)q0 + i] == kWashKeep;
-                    double a[3] = {0.0, 0.0, 0.0};
-                    if (a_ok) {
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) a[j] = ray[3 * ((int64_t)q0 + i) + j];
-                    }
-                    survivors += __popcll(__ballot(a_ok));
-                    pair_rounds<64>(lane, a, a_ok, a, a_ok, 1, 32, best);
-                    for (int tj = ti + 1; tj < nt; ++tj) {
-                        const int jn = tj * 64 + lane;
-                        const bool b_ok = jn < nq && code[(int64_t)q0 + jn] == kWashKeep;
-                        double b[3] = {0.0, 0.0, 0.0};
-                        if (b_ok) {
-#pragma unroll
-                            for (int j = 0; j < 3; ++j) b[j] = ray[3 * ((int64_t)q0 + jn) + j];
-                        }
-                        pair_rounds<64>(lane, a, a_ok, b, b_ok, 0, 63, best);
-                    }
-                }
-                group_widest<64>(best);
-                const double deg = widest_deg(best);
-                const int v = point_verdict(R, survivors, deg);
-                if (lane == 0) {
-                    const int64_t pm = in.pt_map ? in.pt_map[kq] : kq;
-                    max_angle[pm] = deg;
-                    keep_pt[pm] = v == 0;
-                    c[0] += v == 1; c[1] += v == 2; c[2] += v == 0;
-                }
-                for (int i = lane; i < nq; i += 64) {
-                    const int64_t s = (int64_t)q0 + i;
-                    const int64_t so = in.obs_map ? in.obs_map[s] : s;
-                    const bool ko = v == 0 && code[s] == kWashKeep;
-                    keep_obs[so] = ko;
-                    c[3] += ko;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        unsigned v = c[t];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0 && v) atomicAdd(&cnt[t], v);
-    }
-    __syncthreads();
-    if (tid < 4 && cnt[tid]) {
-        const int slot[4] = {kWcPtShort, kWcPtAngle, kWcPtKept, kWcObsKept};
-        atomicAdd(&counts[slot[tid]], (unsigned long long)cnt[tid]);
-    }
-}
 
 }  // namespace
 
@@ -237,7 +132,7 @@ void WashBuffers::alloc(int64_t n_pt_, int64_t n_obs_) {
     counts.alloc(kWcCount);
 }
 
-void ba_wash_eval(const WashInput& in, const sfm_ba_wash_opts& o, WashBuffers& b, hipStream_t s, hipEvent_t* ev,
+void ba_wash_eval(const TrackInput& in, const sfm_ba_wash_opts& o, WashBuffers& b, hipStream_t s, hipEvent_t* ev,
                   double* ms) {
     SFM_REQUIRE(b.n_pt == in.n_pt && b.n_obs == in.n_obs, SFM_ERR_INVALID_ARG, "internal: wash buffers of another size");
     b.counts.zero(s);
@@ -259,7 +154,7 @@ void ba_wash_eval(const WashInput& in, const sfm_ba_wash_opts& o, WashBuffers& b
         SFM_HIP(hipGetLastError());
         const unsigned grid = (unsigned)(((int64_t)in.n_obs + kObsThreads - 1) / kObsThreads);
         SFM_BY_MODEL_ALL(in, hipLaunchKernelGGL(wash_obs_kernel<CM>, dim3(grid), dim3(kObsThreads), 0, s, in,
-                                                o.max_residual_px, (int)o.cheirality, b.blk_pt.p,
+                                                ObsRule{o.max_residual_px, o.cheirality}, b.blk_pt.p,
                                                 reinterpret_cast<double2*>(b.residual.p), b.code.p, b.ray.p,
                                                 b.counts.p));
         SFM_HIP(hipGetLastError());
@@ -268,14 +163,10 @@ void ba_wash_eval(const WashInput& in, const sfm_ba_wash_opts& o, WashBuffers& b
         lap(&ms[0]);
         SFM_HIP(hipEventRecord(ev[0], s));
     }
-    if (in.n_pt > 0) {
-        const int per_block = (kPtThreads / 64) * kPtPerWave;
-        const unsigned grid = (unsigned)(((int64_t)in.n_pt + per_block - 1) / per_block);
-        hipLaunchKernelGGL(wash_point_kernel, dim3(grid), dim3(kPtThreads), 0, s, in,
-                           PointRule{o.min_angle_deg, o.min_track_len}, b.code.p, b.ray.p, b.max_angle.p, b.keep_obs.p,
-                           b.keep_pt.p, b.counts.p);
-        SFM_HIP(hipGetLastError());
-    }
+    if (in.n_pt > 0)
+        track_point_pass(in, WashPoint{PointRule{o.min_angle_deg, o.min_track_len}, b.max_angle.p, b.keep_obs.p,
+                                       b.keep_pt.p},
+                         b.code.p, b.ray.p, b.counts.p, s);
     if (timed) lap(&ms[1]);
 }
 

@@ -1,7 +1,8 @@
 // N-view track triangulation, host side: the options, the serial host entry
-// point (sfm_triangulate_host: a plain loop over the per-point code of
-// tri_point.h) and the one-shot device entry point (sfm_triangulate: the
-// caller's arrays uploaded as they are, the kernels of tri.hip).
+// point (sfm_triangulate_host: per point, tri_point.h's tri_solve_track on
+// one lane and a plain restatement of the point pass) and the one-shot device
+// entry point (sfm_triangulate: a TrackUpload of the caller's arrays, the
+// kernels of tri.hip).
 // SFM_TRI_HOST_ONLY leaves the device entry point out, so that the host path
 // builds with a plain host compiler (tests/cpp/triangulate_test.cpp).
 #include <cmath>
@@ -52,12 +53,21 @@ struct HostOut {
     int64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // sfm_tri_stats order
 };
 
+// tri_solve_track's lanes on the host: one
+struct OneLane {
+    static constexpr int W = 1;
+    static constexpr int g = 0;
+    template <class T>
+    T sum(T v) const { return v; }
+    void best(TriScore&, double (&)[3]) const {}
+};
+
 // every point of the problem, serially (tri.hip's three passes per point)
-template <int CM>
+template <int CM, bool ROBUST>
 void host_points(const sfm_ba_problem& P, const std::vector<CamPre>& cps, const double* intr, const sfm_tri_opts& O,
                  HostOut& out) {
     const int iw = sfm_ba_intr_width(CM);
-    const TriRule rule{O.max_residual_px, O.cheirality};
+    const ObsRule rule{O.max_residual_px, O.cheirality};
     const double nan = std::numeric_limits<double>::quiet_NaN();
     std::vector<double> gram, ray;
     std::vector<uint8_t> bad, code;
@@ -67,10 +77,9 @@ void host_points(const sfm_ba_problem& P, const std::vector<CamPre>& cps, const 
         gram.assign(10 * (size_t)n, 0.0);
         ray.assign(3 * (size_t)n, 0.0);
         bad.assign(n, 0);
-        code.assign(n, kTriBad);
+        code.assign(n, kObsBad);
         auto in_of = [&](int32_t i) { return intr + (int64_t)iw * P.img_intr[P.obs_img[o0 + i]]; };
         auto cp_of = [&](int32_t i) -> const CamPre& { return cps[P.obs_img[o0 + i]]; };
-        int32_t m = 0;
         for (int32_t i = 0; i < n; ++i) {
             double b[3], G[10], d[3];
             bad[i] = !tri_bearing<CM>(in_of(i), P.obs_uv[2 * (o0 + i)], P.obs_uv[2 * (o0 + i) + 1], b);
@@ -78,94 +87,41 @@ void host_points(const sfm_ba_problem& P, const std::vector<CamPre>& cps, const 
                 ++out.c[5];
                 continue;
             }
-            ++m;
             tri_gram(cp_of(i), b, G);
             tri_world_ray(cp_of(i), b, d);
             std::memcpy(&gram[10 * (size_t)i], G, sizeof G);
             std::memcpy(&ray[3 * (size_t)i], d, sizeof d);
         }
+        auto good = [&](int32_t i) { return bad[i] == 0; };
         auto add_gram = [&](double (&G)[10], int32_t i) {
             for (int e = 0; e < 10; ++e) G[e] += gram[10 * (size_t)i + e];
         };
         auto judge = [&](int32_t i, const double (&X)[3], double& r0, double& r1) {
-            return tri_judge<CM>(cp_of(i), in_of(i), X, P.obs_uv[2 * (o0 + i)], P.obs_uv[2 * (o0 + i) + 1], rule, r0,
+            return judge_obs<CM>(cp_of(i), in_of(i), X, P.obs_uv[2 * (o0 + i)], P.obs_uv[2 * (o0 + i) + 1], rule, r0,
                                  r1);
         };
-        uint8_t fin = kTriNoSolve;
-        double X[3] = {0.0, 0.0, 0.0};
-        if (O.method == SFM_TRI_LINEAR) {
-            if (m >= 2) {
-                double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-                for (int32_t i = 0; i < n; ++i)
-                    if (!bad[i]) add_gram(G, i);
-                fin = tri_solve4(G, X) ? kTriSolved : kTriInfinite;
-            }
-        } else {
-            auto img_of = [&](int32_t i) { return bad[i] ? -1 : P.obs_img[o0 + i]; };
-            int64_t npairs = 0;
-            if (m >= 2)
-                for (int32_t a = 0; a < n; ++a) npairs += tri_row_pairs(n, a, img_of);
-            const int64_t H = npairs < O.max_hypotheses ? npairs : (int64_t)O.max_hypotheses;
-            TriScore best{-1, 0.0, 0};
-            double bX[3] = {0.0, 0.0, 0.0};
-            for (int64_t h = 0; h < H; ++h) {
-                int32_t a, b;
-                tri_unrank(n, img_of, tri_hyp_rank(h, npairs, O.max_hypotheses), a, b);
-                double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, Xh[3] = {0.0, 0.0, 0.0};
-                add_gram(G, a);
-                add_gram(G, b);
-                TriScore sc{0, 0.0, (int32_t)h};
-                if (tri_solve4(G, Xh)) {
-                    for (int32_t i = 0; i < n; ++i) {
-                        if (bad[i]) continue;
-                        double r0, r1;
-                        if (judge(i, Xh, r0, r1) == kTriKeep) {
-                            ++sc.cnt;
-                            sc.ssq += r0 * r0 + r1 * r1;
-                        }
-                    }
-                }
-                if (tri_better(sc, best)) {
-                    best = sc;
-                    for (int j = 0; j < 3; ++j) bX[j] = Xh[j];
-                }
-            }
-            if (best.cnt >= 2) {
-                double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-                for (int32_t i = 0; i < n; ++i) {
-                    if (bad[i]) continue;
-                    double r0, r1;
-                    if (judge(i, bX, r0, r1) == kTriKeep) add_gram(G, i);
-                }
-                fin = tri_solve4(G, X) ? kTriSolved : kTriInfinite;
-            }
-        }
-        // the final judgement
+        auto img_of = [&](int32_t i) { return bad[i] ? -1 : P.obs_img[o0 + i]; };
         int32_t survivors = 0;
-        for (int32_t i = 0; i < n; ++i) {
-            double r0 = nan, r1 = nan;
-            if (!bad[i]) {
-                if (fin == kTriSolved) {
-                    code[i] = judge(i, X, r0, r1);
-                    out.c[6] += code[i] == kTriDepth;
-                    out.c[7] += code[i] == kTriResidual;
-                    survivors += code[i] == kTriKeep;
-                } else {
-                    code[i] = kTriNoPoint;
-                }
-            }
+        auto emit = [&](int32_t i, uint8_t cd, double r0, double r1) {
+            code[i] = cd;
+            out.c[6] += cd == kObsDepth;
+            out.c[7] += cd == kObsResidual;
+            survivors += cd == kObsKeep;
             if (out.residual) {
                 out.residual[2 * (o0 + i)] = r0;
                 out.residual[2 * (o0 + i) + 1] = r1;
             }
-        }
+        };
+        double X[3];
+        const uint8_t fin =
+            tri_solve_track<ROBUST>(OneLane{}, n, O.max_hypotheses, good, add_gram, judge, img_of, emit, X);
         // the widest angle between two kept rays, atan2(|a x b|, a.b)
         double deg = 0.0;
         for (int32_t i = 0; i < n; ++i) {
-            if (code[i] != kTriKeep) continue;
+            if (code[i] != kObsKeep) continue;
             const double* a = &ray[3 * (size_t)i];
             for (int32_t j = i + 1; j < n; ++j) {
-                if (code[j] != kTriKeep) continue;
+                if (code[j] != kObsKeep) continue;
                 const double* b = &ray[3 * (size_t)j];
                 const double c0 = a[1] * b[2] - a[2] * b[1], c1 = a[2] * b[0] - a[0] * b[2],
                              c2 = a[0] * b[1] - a[1] * b[0];
@@ -185,7 +141,7 @@ void host_points(const sfm_ba_problem& P, const std::vector<CamPre>& cps, const 
         if (out.X)
             for (int j = 0; j < 3; ++j) out.X[3 * p + j] = st == SFM_TRI_OK ? X[j] : nan;
         for (int32_t i = 0; i < n; ++i) {
-            const bool ko = st == SFM_TRI_OK && code[i] == kTriKeep;
+            const bool ko = st == SFM_TRI_OK && code[i] == kObsKeep;
             out.c[4] += ko;
             if (out.keep_obs) out.keep_obs[o0 + i] = ko;
         }
@@ -204,9 +160,13 @@ extern "C" int sfm_triangulate_host(const sfm_ba_problem* prob, const double* ex
         std::vector<CamPre> cps((size_t)prob->n_img);
         for (int32_t i = 0; i < prob->n_img; ++i) cps[i] = make_campre(extr + 6 * (size_t)i);
         HostOut out{X, status, keep_obs, residual};
-        if (prob->camera_model == SFM_CAM_RADIAL3) host_points<SFM_CAM_RADIAL3>(*prob, cps, intr, O, out);
-        else if (prob->camera_model == SFM_CAM_SNAVELY) host_points<SFM_CAM_SNAVELY>(*prob, cps, intr, O, out);
-        else host_points<SFM_CAM_PINHOLE>(*prob, cps, intr, O, out);
+        auto by_method = [&](auto cm) {
+            if (O.method == SFM_TRI_ROBUST) host_points<decltype(cm)::value, true>(*prob, cps, intr, O, out);
+            else host_points<decltype(cm)::value, false>(*prob, cps, intr, O, out);
+        };
+        if (prob->camera_model == SFM_CAM_RADIAL3) by_method(std::integral_constant<int, SFM_CAM_RADIAL3>{});
+        else if (prob->camera_model == SFM_CAM_SNAVELY) by_method(std::integral_constant<int, SFM_CAM_SNAVELY>{});
+        else by_method(std::integral_constant<int, SFM_CAM_PINHOLE>{});
         if (stats) {
             stats->n_pt_ok = out.c[0]; stats->n_pt_short = out.c[1]; stats->n_pt_angle = out.c[2];
             stats->n_pt_infinite = out.c[3]; stats->n_obs_kept = out.c[4]; stats->n_obs_bad = out.c[5];
@@ -226,25 +186,7 @@ extern "C" int sfm_triangulate(sfm_ctx* ctx, const sfm_ba_problem* prob, const d
         validate_problem(*prob);
         CtxScope scope_(ctx);
         hipStream_t s = ctx->stream;
-        const int iw = sfm_ba_intr_width(prob->camera_model);
-        const size_t np = (size_t)prob->n_pt, no = (size_t)prob->n_obs;
-        HostVec<int32_t> off(np + 1);
-        for (size_t p = 0; p <= np; ++p) off[p] = (int32_t)prob->pt_offsets[p];
-        DBuf<int32_t> d_off, d_img, d_img_intr;
-        DBuf<double> d_uv, d_extr, d_intr;
-        DBuf<CamPre> d_cp;
-        d_off.alloc(np + 1); d_off.upload(off.data(), np + 1, s);
-        d_img.alloc(no); d_img.upload(prob->obs_img, no, s);
-        d_uv.alloc(2 * no); d_uv.upload(prob->obs_uv, 2 * no, s);
-        d_img_intr.alloc(prob->n_img); d_img_intr.upload(prob->img_intr, prob->n_img, s);
-        d_extr.alloc(6 * (size_t)prob->n_img); d_extr.upload(extr, 6 * (size_t)prob->n_img, s);
-        d_intr.alloc((size_t)iw * prob->n_intr); d_intr.upload(intr, (size_t)iw * prob->n_intr, s);
-        d_cp.alloc(prob->n_img);
-        TriInput in;
-        in.n_pt = (int32_t)np; in.n_obs = (int32_t)no;
-        in.cam_model = prob->camera_model; in.iw = iw;
-        in.pt_off = d_off.p; in.obs_img = d_img.p; in.obs_uv = d_uv.p; in.img_intr = d_img_intr.p;
-        in.cp = d_cp.p; in.intr = d_intr.p;
+        TrackUpload up(*prob, extr, intr, nullptr, s);
         TriBuffers b;
         b.alloc(prob->n_pt, prob->n_obs);
         hipEvent_t* ev = nullptr;
@@ -253,8 +195,8 @@ extern "C" int sfm_triangulate(sfm_ctx* ctx, const sfm_ba_problem* prob, const d
             SFM_HIP(hipStreamSynchronize(s));
             SFM_HIP(hipEventRecord(ev[0], s));
         }
-        ba_campre(d_extr.p, prob->n_img, d_cp.p, s);
-        tri_eval(in, O, b, s);
+        ba_campre(up.extr.p, prob->n_img, up.cp.p, s);
+        tri_eval(up.in, O, b, s);
         if (ev) {
             SFM_HIP(hipEventRecord(ev[1], s));
             SFM_HIP(hipEventSynchronize(ev[1]));

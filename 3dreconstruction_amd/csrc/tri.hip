@@ -1,24 +1,24 @@
 // N-view track triangulation for CDNA4 (gfx950), fp64: OpenMVG's
 // ComputeStructureFromKnownPoses step (TriangulateNViewAlgebraic, and a
 // deterministic stand-in for its robust track triangulation), restated;
-// semantics in include/sfmcore.h, arithmetic in tri_point.h.
+// semantics in include/sfmcore.h, the per-track algorithm in tri_point.h.
 //
 //   obs pass    one lane per observation: the unit bearing b of the pixel (20
 //               undistortion iterations for the radial models), the 10 unique
 //               entries of C'C, C = (I - b b')[R|t], the world ray R' b and the
 //               bad flag.  Streaming: reads image 4 B + pixel 16 B, writes
 //               80 B + 24 B + 1 B per observation.
-//   solve pass  a point of <= kTriGroup observations takes a lane group (64 /
-//               kTriGroup points per wave), a longer one a whole wave.
-//               LINEAR: M = sum of the good observations' Grams in observation
-//               order, one 4x4 Jacobi.  ROBUST: a lane per two-view hypothesis
-//               (Jacobi of two Grams, judged on every observation of the track
-//               in order), the best score by a total order through shuffles,
+//   solve pass  a point of <= kTrackGroup observations takes a lane group (64 /
+//               kTrackGroup points per wave), a longer one a whole wave, and
+//               runs tri_solve_track (tri_point.h) over its lanes: LINEAR one
+//               4x4 Jacobi of the summed Grams; ROBUST a lane per two-view
+//               hypothesis, the best score by a total order through shuffles,
 //               then the N-view refit over its inliers.  Last, a lane per
 //               observation: residual and reject code at the final X.
-//   point pass  the wash's point pass over those codes and the measured rays:
-//               survivors, the widest angle between two of them, the status;
-//               X = NaN and keep_obs = 0 for a point that is not OK.
+//   point pass  track_point_kernel (track.h) with the TriPoint policy below,
+//               over those codes and the measured rays: survivors, the widest
+//               angle between two of them, the status; X = NaN and keep_obs =
+//               0 for a point that is not OK.
 //
 // The staged Grams and rays live in a global scratch at every track length
 // (a point's 104 B per observation are read back by its own lane group right
@@ -33,11 +33,9 @@ namespace sfm {
 namespace {
 
 constexpr int kObsThreads = 256;
-constexpr int kPtThreads = 256;
-constexpr int kPtPerWave = 64 / kTriGroup;
 
 template <int CM>
-__global__ __launch_bounds__(kObsThreads) void tri_obs_kernel(TriInput in, double* __restrict__ gram,
+__global__ __launch_bounds__(kObsThreads) void tri_obs_kernel(TrackInput in, double* __restrict__ gram,
                                                               double* __restrict__ ray, uint8_t* __restrict__ badf,
                                                               unsigned long long* __restrict__ counts) {
     const int64_t s = (int64_t)blockIdx.x * kObsThreads + threadIdx.x;
@@ -70,79 +68,14 @@ __device__ __forceinline__ T group_sum(T v) {
     return v;
 }
 
-struct SolveOpts {
-    TriRule rule;
-    int32_t max_hyp;
-};
-
-// the judgement of observation i of a point (first observation o0) at X
-template <int CM>
-__device__ __forceinline__ uint8_t judge_at(const TriInput& in, int64_t s, const double (&X)[3], const TriRule& R,
-                                            double& r0, double& r1) {
-    const int32_t img = in.obs_img[s];
-    const double2 uv = reinterpret_cast<const double2*>(in.obs_uv)[s];
-    return tri_judge<CM>(in.cp[img], in.intr + (int64_t)in.iw * in.img_intr[img], X, uv.x, uv.y, R, r0, r1);
-}
-
-// One point by the W lanes of a group (every lane of the wave calls it; a
-// group without a point has n = 0).  g: the lane within the group.
-template <int CM, bool ROBUST, int W>
-__device__ __forceinline__ void solve_point(const TriInput& in, const SolveOpts& O, bool has, int64_t k, int32_t o0,
-                                            int32_t n, int g, const double* __restrict__ gram,
-                                            const uint8_t* __restrict__ badf, uint8_t* __restrict__ code, double* __restrict__ Xs,
-                                            uint8_t* __restrict__ solved, double2* __restrict__ residual,
-                                            unsigned (&c)[2]) {
-    auto good = [&](int32_t i) { return badf[(int64_t)o0 + i] == 0; };
-    int32_t m_loc = 0;
-    for (int32_t i = g; i < n; i += W) m_loc += good(i);
-    const int32_t m = group_sum<W>(m_loc);
-    uint8_t fin = kTriNoSolve;
-    double X[3] = {0.0, 0.0, 0.0};
-    // M = the Grams of the chosen observations, summed in observation order
-    auto add_gram = [&](double (&G)[10], int32_t i) {
-        const double* gp = gram + 10 * ((int64_t)o0 + i);
-#pragma unroll
-        for (int e = 0; e < 10; ++e) G[e] += gp[e];
-    };
-    if constexpr (!ROBUST) {
-        if (m >= 2) {
-            double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (int32_t i = 0; i < n; ++i)
-                if (good(i)) add_gram(G, i);
-            fin = tri_solve4(G, X) ? kTriSolved : kTriInfinite;
-        }
-    } else {
-        auto img_of = [&](int32_t i) { return good(i) ? in.obs_img[(int64_t)o0 + i] : -1; };
-        long long np_loc = 0;
-        if (m >= 2)
-            for (int32_t a = g; a < n; a += W) np_loc += tri_row_pairs(n, a, img_of);
-        const long long npairs = group_sum<W>(np_loc);
-        const long long H = npairs < O.max_hyp ? npairs : (long long)O.max_hyp;
-        TriScore best{-1, 0.0, 0};
-        double bX[3] = {0.0, 0.0, 0.0};
-        for (long long h = g; h < H; h += W) {
-            int32_t a, b;
-            tri_unrank(n, img_of, tri_hyp_rank(h, npairs, O.max_hyp), a, b);
-            double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, Xh[3] = {0.0, 0.0, 0.0};
-            add_gram(G, a);
-            add_gram(G, b);
-            TriScore sc{0, 0.0, (int32_t)h};
-            if (tri_solve4(G, Xh)) {
-                for (int32_t i = 0; i < n; ++i) {
-                    if (!good(i)) continue;
-                    double r0, r1;
-                    if (judge_at<CM>(in, (int64_t)o0 + i, Xh, O.rule, r0, r1) == kTriKeep) {
-                        ++sc.cnt;
-                        sc.ssq += r0 * r0 + r1 * r1;
-                    }
-                }
-            }
-            if (tri_better(sc, best)) {
-                best = sc;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) bX[j] = Xh[j];
-            }
-        }
+// tri_solve_track's lanes: the W lanes of a wave that share a point
+template <int W_>
+struct GroupLanes {
+    static constexpr int W = W_;
+    int g;   // the lane within the group
+    template <class T>
+    __device__ T sum(T v) const { return group_sum<W>(v); }
+    __device__ void best(TriScore& best, double (&bX)[3]) const {
 #pragma unroll
         for (int o = W / 2; o > 0; o >>= 1) {
             TriScore ot{__shfl_xor(best.cnt, o, W), __shfl_xor(best.ssq, o, W), __shfl_xor(best.h, o, W)};
@@ -152,35 +85,45 @@ __device__ __forceinline__ void solve_point(const TriInput& in, const SolveOpts&
                 bX[0] = x0; bX[1] = x1; bX[2] = x2;
             }
         }
-        if (best.cnt >= 2) {   // the refit over the winner's inliers (the same in every lane)
-            double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (int32_t i = 0; i < n; ++i) {
-                if (!good(i)) continue;
-                double r0, r1;
-                if (judge_at<CM>(in, (int64_t)o0 + i, bX, O.rule, r0, r1) == kTriKeep) add_gram(G, i);
-            }
-            fin = tri_solve4(G, X) ? kTriSolved : kTriInfinite;
-        }
     }
-    // the final judgement, a lane per observation
-    const double nan = __builtin_nan("");
-    for (int32_t i = g; i < n; i += W) {
+};
+
+struct SolveOpts {
+    ObsRule rule;
+    int32_t max_hyp;
+};
+
+// One point (first observation o0, n of them) by the W lanes of a group: every
+// lane of the wave calls it; a group without a point has n = 0.
+template <int CM, bool ROBUST, int W>
+__device__ __forceinline__ void solve_point(const TrackInput& in, const SolveOpts& O, bool has, int64_t k, int32_t o0,
+                                            int32_t n, int g, const double* __restrict__ gram,
+                                            const uint8_t* __restrict__ badf, uint8_t* __restrict__ code, double* __restrict__ Xs,
+                                            uint8_t* __restrict__ solved, double2* __restrict__ residual,
+                                            unsigned (&c)[2]) {
+    auto good = [&](int32_t i) { return badf[(int64_t)o0 + i] == 0; };
+    auto add_gram = [&](double (&G)[10], int32_t i) {
+        const double* gp = gram + 10 * ((int64_t)o0 + i);
+#pragma unroll
+        for (int e = 0; e < 10; ++e) G[e] += gp[e];
+    };
+    auto judge = [&](int32_t i, const double (&X)[3], double& r0, double& r1) {
         const int64_t s = (int64_t)o0 + i;
-        uint8_t cd = kTriBad;
-        double r0 = nan, r1 = nan;
-        if (badf[s] == 0) {
-            if (fin == kTriSolved) {
-                cd = judge_at<CM>(in, s, X, O.rule, r0, r1);
-                c[0] += cd == kTriDepth;
-                c[1] += cd == kTriResidual;
-            } else {
-                cd = kTriNoPoint;
-            }
-        }
-        residual[s] = make_double2(r0, r1);
-        code[s] = cd;
-    }
+        const int32_t img = in.obs_img[s];
+        const double2 uv = reinterpret_cast<const double2*>(in.obs_uv)[s];
+        return judge_obs<CM>(in.cp[img], in.intr + (int64_t)in.iw * in.img_intr[img], X, uv.x, uv.y, O.rule, r0, r1);
+    };
+    auto img_of = [&](int32_t i) { return good(i) ? in.obs_img[(int64_t)o0 + i] : -1; };
+    auto out = [&](int32_t i, uint8_t cd, double r0, double r1) {
+        c[0] += cd == kObsDepth;
+        c[1] += cd == kObsResidual;
+        residual[(int64_t)o0 + i] = make_double2(r0, r1);
+        code[(int64_t)o0 + i] = cd;
+    };
+    double X[3];
+    const uint8_t fin = tri_solve_track<ROBUST>(GroupLanes<W>{g}, n, O.max_hyp, good, add_gram, judge, img_of, out, X);
     if (has && g == 0) {
+        const double nan = __builtin_nan("");
 #pragma unroll
         for (int j = 0; j < 3; ++j) Xs[3 * k + j] = fin == kTriSolved ? X[j] : nan;
         solved[k] = fin;
@@ -188,7 +131,7 @@ __device__ __forceinline__ void solve_point(const TriInput& in, const SolveOpts&
 }
 
 template <int CM, bool ROBUST>
-__global__ __launch_bounds__(kPtThreads) void tri_solve_kernel(TriInput in, SolveOpts O,
+__global__ __launch_bounds__(kPtThreads) void tri_solve_kernel(TrackInput in, SolveOpts O,
                                                                const double* __restrict__ gram,
                                                                const uint8_t* __restrict__ badf,
                                                                uint8_t* __restrict__ code, double* __restrict__ Xs, uint8_t* __restrict__ solved,
@@ -197,13 +140,13 @@ __global__ __launch_bounds__(kPtThreads) void tri_solve_kernel(TriInput in, Solv
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t kw = ((int64_t)blockIdx.x * (kPtThreads / 64) + wave) * kPtPerWave;   // the wave's first point
     unsigned c[2] = {0, 0};
-    const int grp = lane / kTriGroup, g = lane % kTriGroup;
+    const int grp = lane / kTrackGroup, g = lane % kTrackGroup;
     const int64_t k = kw + grp;
     const bool has = k < in.n_pt;
     const int32_t o0 = has ? in.pt_off[k] : 0;
     const int32_t n = has ? in.pt_off[k + 1] - o0 : 0;
-    if (!__any(n > kTriGroup)) {
-        solve_point<CM, ROBUST, kTriGroup>(in, O, has, k, o0, n, g, gram, badf, code, Xs, solved, residual, c);
+    if (!__any(n > kTrackGroup)) {
+        solve_point<CM, ROBUST, kTrackGroup>(in, O, has, k, o0, n, g, gram, badf, code, Xs, solved, residual, c);
     } else {
         for (int q = 0; q < kPtPerWave; ++q) {
             const int64_t kq = kw + q;
@@ -220,116 +163,42 @@ __global__ __launch_bounds__(kPtThreads) void tri_solve_kernel(TriInput in, Solv
     }
 }
 
-struct PointRule {
-    double min_angle_deg;
-    int32_t min_track;
-};
-// the first rule that applies (SFM_TRI_* status)
-__device__ __forceinline__ int point_status(const PointRule& R, uint8_t fin, int survivors, double deg) {
-    if (fin == kTriNoSolve) return SFM_TRI_SHORT;
-    if (fin == kTriInfinite) return SFM_TRI_INFINITE;
-    if (survivors < R.min_track) return SFM_TRI_SHORT;
-    if (R.min_angle_deg > 0.0 && deg < R.min_angle_deg) return SFM_TRI_ANGLE;
-    return SFM_TRI_OK;
-}
-
-// The wash's point pass (ba_wash.hip) over the triangulation's codes and the
-// measured rays.
-__global__ __launch_bounds__(kPtThreads) void tri_point_kernel(TriInput in, PointRule R,
-                                                               const uint8_t* __restrict__ code,
-                                                               const double* __restrict__ ray,
-                                                               const uint8_t* __restrict__ solved,
-                                                               double* __restrict__ X, uint8_t* __restrict__ status,
-                                                               uint8_t* __restrict__ keep_obs,
-                                                               unsigned long long* __restrict__ counts) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t kw = ((int64_t)blockIdx.x * (kPtThreads / 64) + wave) * kPtPerWave;
-    unsigned c[5] = {0, 0, 0, 0, 0};   // ok, short, angle, infinite, observations kept
-    const double nan = __builtin_nan("");
-    auto finish = [&](int64_t kk, int v) {   // one lane per point
-        status[kk] = (uint8_t)v;
+// The triangulation's side of the point pass (track.h), over the codes of the
+// solve pass and the measured rays: the verdict is an SFM_TRI_* status, what
+// the solve left first, then the point rule; status and keep_obs go out in
+// the caller's order, and X = NaN for a point that is not OK.
+static_assert(SFM_TRI_OK == 0 && SFM_TRI_SHORT == 1 && SFM_TRI_ANGLE == 2, "point_rule's verdicts are the statuses");
+struct TriPoint {
+    static constexpr int kCounts = 5;   // ok, short, angle, infinite, observations kept
+    __device__ static int slot(int t) {
+        const int s[kCounts] = {kTcPtOk, kTcPtShort, kTcPtAngle, kTcPtInfinite, kTcObsKept};
+        return s[t];
+    }
+    PointRule rule;
+    const uint8_t* __restrict__ solved;
+    double* __restrict__ X;
+    uint8_t* __restrict__ status;
+    uint8_t* __restrict__ keep_obs;
+    __device__ int verdict(int64_t k, int survivors, double deg) const {
+        const uint8_t fin = solved[k];
+        if (fin == kTriNoSolve) return SFM_TRI_SHORT;
+        if (fin == kTriInfinite) return SFM_TRI_INFINITE;
+        return point_rule(rule, survivors, deg);
+    }
+    __device__ void point(const TrackInput&, int64_t k, int v, double, unsigned (&c)[kCounts]) const {
+        status[k] = (uint8_t)v;
         if (v != SFM_TRI_OK) {
+            const double nan = __builtin_nan("");
 #pragma unroll
-            for (int j = 0; j < 3; ++j) X[3 * kk + j] = nan;
+            for (int j = 0; j < 3; ++j) X[3 * k + j] = nan;
         }
         c[0] += v == SFM_TRI_OK; c[1] += v == SFM_TRI_SHORT; c[2] += v == SFM_TRI_ANGLE; c[3] += v == SFM_TRI_INFINITE;
-    };
-    const int grp = lane / kTriGroup, g = lane % kTriGroup;
-    const int64_t k = kw + grp;
-    const bool has = k < in.n_pt;
-    const int32_t o0 = has ? in.pt_off[k] : 0;
-    const int32_t n = has ? in.pt_off[k + 1] - o0 : 0;
-    if (!__any(n > kTriGroup)) {
-        // ---- a lane group per point ----
-        const bool mine = g < n;
-        const int64_t s = (int64_t)o0 + g;
-        const bool ok = mine && code[s] == kTriKeep;
-        double a[3] = {0.0, 0.0, 0.0};
-        if (ok) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) a[j] = ray[3 * s + j];
-        }
-        Widest best{0.0, 1.0};
-        pair_rounds<kTriGroup>(g, a, ok, a, ok, 1, kTriGroup / 2, best);
-        group_widest<kTriGroup>(best);
-        const unsigned long long mk = __ballot(ok);
-        const int survivors = __popcll((mk >> (grp * kTriGroup)) & ((1ull << kTriGroup) - 1));
-        const int v = point_status(R, has ? solved[k] : (uint8_t)kTriNoSolve, survivors, widest_deg(best));
-        if (has && g == 0) finish(k, v);
-        if (mine) {
-            const bool ko = v == SFM_TRI_OK && ok;
-            keep_obs[s] = ko;
-            c[4] += ko;
-        }
-    } else {
-        // ---- a wave per point, pairs in rounds of 64 ----
-        for (int q = 0; q < kPtPerWave; ++q) {
-            const int64_t kq = kw + q;
-            if (kq >= in.n_pt) break;   // (wave-uniform)
-            const int32_t q0 = in.pt_off[kq];
-            const int32_t nq = in.pt_off[kq + 1] - q0;
-            const int nt = (nq + 63) / 64;
-            Widest best{0.0, 1.0};
-            int survivors = 0;
-            for (int ti = 0; ti < nt; ++ti) {
-                const int i = ti * 64 + lane;
-                const bool a_ok = i < nq && code[(int64_t)q0 + i] == kTriKeep;
-                double a[3] = {0.0, 0.0, 0.0};
-                if (a_ok) {
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) a[j] = ray[3 * ((int64_t)q0 + i) + j];
-                }
-                survivors += __popcll(__ballot(a_ok));
-                pair_rounds<64>(lane, a, a_ok, a, a_ok, 1, 32, best);
-                for (int tj = ti + 1; tj < nt; ++tj) {
-                    const int jn = tj * 64 + lane;
-                    const bool b_ok = jn < nq && code[(int64_t)q0 + jn] == kTriKeep;
-                    double b[3] = {0.0, 0.0, 0.0};
-                    if (b_ok) {
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) b[j] = ray[3 * ((int64_t)q0 + jn) + j];
-                    }
-                    pair_rounds<64>(lane, a, a_ok, b, b_ok, 0, 63, best);
-                }
-            }
-            group_widest<64>(best);
-            const int v = point_status(R, solved[kq], survivors, widest_deg(best));
-            if (lane == 0) finish(kq, v);
-            for (int i = lane; i < nq; i += 64) {
-                const int64_t s = (int64_t)q0 + i;
-                const bool ko = v == SFM_TRI_OK && code[s] == kTriKeep;
-                keep_obs[s] = ko;
-                c[4] += ko;
-            }
-        }
     }
-    const int slot[5] = {kTcPtOk, kTcPtShort, kTcPtAngle, kTcPtInfinite, kTcObsKept};
-#pragma unroll
-    for (int t = 0; t < 5; ++t) {
-        const unsigned v = group_sum<64>(c[t]);
-        if (lane == 0 && v) atomicAdd(&counts[slot[t]], (unsigned long long)v);
+    __device__ void obs(const TrackInput&, int64_t s, bool keep, unsigned (&c)[kCounts]) const {
+        keep_obs[s] = keep;
+        c[4] += keep;
     }
-}
+};
 
 }  // namespace
 
@@ -348,7 +217,7 @@ void TriBuffers::alloc(int64_t n_pt_, int64_t n_obs_) {
     counts.alloc(kTcCount);
 }
 
-void tri_eval(const TriInput& in, const sfm_tri_opts& o, TriBuffers& b, hipStream_t s) {
+void tri_eval(const TrackInput& in, const sfm_tri_opts& o, TriBuffers& b, hipStream_t s) {
     SFM_REQUIRE(b.n_pt == in.n_pt && b.n_obs == in.n_obs, SFM_ERR_INVALID_ARG, "internal: triangulation buffers of another size");
     b.counts.zero(s);
     if (in.n_obs > 0) {
@@ -358,9 +227,8 @@ void tri_eval(const TriInput& in, const sfm_tri_opts& o, TriBuffers& b, hipStrea
         SFM_HIP(hipGetLastError());
     }
     if (in.n_pt > 0) {
-        const int per_block = (kPtThreads / 64) * kPtPerWave;
-        const unsigned grid = (unsigned)(((int64_t)in.n_pt + per_block - 1) / per_block);
-        const SolveOpts O{TriRule{o.max_residual_px, o.cheirality}, o.max_hypotheses};
+        const unsigned grid = point_grid(in.n_pt);
+        const SolveOpts O{ObsRule{o.max_residual_px, o.cheirality}, o.max_hypotheses};
         by_flag(o.method == SFM_TRI_ROBUST, [&](auto robust) {
             SFM_BY_MODEL_ALL(in, hipLaunchKernelGGL((tri_solve_kernel<CM, decltype(robust)::value>), dim3(grid),
                                                     dim3(kPtThreads), 0, s, in, O, b.gram.p, b.bad.p, b.code.p, b.X.p,
@@ -368,10 +236,9 @@ void tri_eval(const TriInput& in, const sfm_tri_opts& o, TriBuffers& b, hipStrea
                                                     b.counts.p));
         });
         SFM_HIP(hipGetLastError());
-        hipLaunchKernelGGL(tri_point_kernel, dim3(grid), dim3(kPtThreads), 0, s, in,
-                           PointRule{o.min_angle_deg, o.min_track_len}, b.code.p, b.ray.p, b.solved.p, b.X.p,
-                           b.status.p, b.keep_obs.p, b.counts.p);
-        SFM_HIP(hipGetLastError());
+        track_point_pass(in, TriPoint{PointRule{o.min_angle_deg, o.min_track_len}, b.solved.p, b.X.p, b.status.p,
+                                      b.keep_obs.p},
+                         b.code.p, b.ray.p, b.counts.p, s);
     }
 }
 

@@ -1,11 +1,13 @@
-// N-view track triangulation, the per-point pieces (include/sfmcore.h,
-// "Track triangulation"), written once for the device kernels
+// N-view track triangulation, per track (include/sfmcore.h, "Track
+// triangulation"), written once for the device kernels
 // (tri.hip) and the serial host loop (tri.cpp, sfm_triangulate_host): the
 // bearing of a pixel, the Gram C'C of an observation, the 4x4 eigen solve, the
-// judgement of an observation at a point, the hypothesis score and the pair
-// unranking.  Host and device run the same statements; only the reciprocal
-// of the depth differs (the wash's rcp_nr on the device, a division on the
-// host), so the two agree to rounding, not bit for bit.
+// hypothesis score, the pair unranking, and tri_solve_track, the LINEAR /
+// ROBUST algorithm over them, written for the W lanes that share a track (16
+// or 64 on the device, 1 on the host).  The judgement of an observation at a
+// point is track.h's judge_obs.  Host and device run the same statements;
+// only the reciprocal of the depth differs (track.h, depth_rcp), so the two
+// agree to rounding, not bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,33 +16,15 @@
 
 #include "ba_cand.h"
 #include "ba_types.h"
-#if defined(__HIPCC__)
-#include "ba_wash_device.h"
-#endif
+#include "track.h"
 
 namespace sfm {
 namespace {
 
-#if !defined(__HIPCC__)   // a plain host compiler (the stand-alone host test)
-using std::fabs;
-using std::sqrt;
-#endif
-
-// finite: neither NaN nor an infinity (one definition for host and device)
-__host__ __device__ inline bool tri_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
-
-// reject code of an observation at a point (the wash's first three, then the
-// triangulation's own)
-enum : uint8_t { kTriKeep = 0, kTriDepth = 1, kTriResidual = 2, kTriBad = 3, kTriNoPoint = 4 };
 // what a point's solve left (the point pass turns it into a status)
 enum : uint8_t { kTriSolved = 0, kTriNoSolve = 1, kTriInfinite = 3 };
 // undistortion: fixed-point iterations p_u <- p_d / c(|p_u|^2)
 constexpr int kTriUndistortIters = 20;
-
-struct TriRule {
-    double max_residual_px;
-    int32_t cheirality;
-};
 
 // the radial factor of a model at r2 = |p_u|^2 (include/sfmcore.h)
 template <int CM>
@@ -82,7 +66,7 @@ __host__ __device__ inline bool tri_bearing(const double* in, double u, double v
     }
     const double n = sqrt(x * x + y * y + 1.0);
     b[0] = x / n; b[1] = y / n; b[2] = z / n;
-    return tri_finite(b[0]) && tri_finite(b[1]) && tri_finite(b[2]);
+    return track_finite(b[0]) && track_finite(b[1]) && track_finite(b[2]);
 }
 
 // The 10 unique entries (rows 0..3, columns >= row) of C'C, C = (I - b b')[R|t]
@@ -177,59 +161,7 @@ __host__ __device__ inline bool tri_solve4(const double (&G)[10], double (&X)[3]
     if (!(fabs(v[3]) > 1e-12)) return false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) X[a] = v[a] / v[3];
-    return tri_finite(X[0]) && tri_finite(X[1]) && tri_finite(X[2]);
-}
-
-// P = R X + t and the unweighted residual of the model: the wash's own
-// function on the device; on the host the same formulas with a division.
-template <int CM>
-__host__ __device__ inline void tri_project(const CamPre& cp, const double* in, const double (&X)[3], double u0,
-                                            double u1, double (&P)[3], double& r0, double& r1) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    wash_project<CM>(cp, in, X, u0, u1, P, r0, r1);
-#else
-    const double* u = cp.u;
-    const double cr0 = u[1] * X[2] - u[2] * X[1], cr1 = u[2] * X[0] - u[0] * X[2],
-                 cr2 = u[0] * X[1] - u[1] * X[0];
-    if (cp.small != 0.0) {
-        P[0] = X[0] + cr0; P[1] = X[1] + cr1; P[2] = X[2] + cr2;
-    } else {
-        const double tmp = (u[0] * X[0] + u[1] * X[1] + u[2] * X[2]) * cp.omc;
-        P[0] = X[0] * cp.c + cr0 * cp.s + u[0] * tmp;
-        P[1] = X[1] * cp.c + cr1 * cp.s + u[1] * tmp;
-        P[2] = X[2] * cp.c + cr2 * cp.s + u[2] * tmp;
-    }
-    P[0] += cp.t[0]; P[1] += cp.t[1]; P[2] += cp.t[2];
-    const double iz = 1.0 / P[2];
-    if constexpr (CM == SFM_CAM_RADIAL3) {
-        const double xu = P[0] * iz, yu = P[1] * iz;
-        const double rc = tri_radial<CM>(in, xu * xu + yu * yu);
-        r0 = in[1] + in[0] * (xu * rc) - u0;
-        r1 = in[2] + in[0] * (yu * rc) - u1;
-    } else if constexpr (CM == SFM_CAM_SNAVELY) {
-        const double xp = -P[0] * iz, yp = -P[1] * iz;
-        const double d = tri_radial<CM>(in, xp * xp + yp * yp);
-        r0 = in[0] * d * xp - u0;
-        r1 = in[0] * d * yp - u1;
-    } else {
-        const double x = P[0] * iz, y = P[1] * iz;
-        r0 = in[0] * x + in[2] - u0;
-        r1 = in[1] * y + in[3] - u1;
-    }
-#endif
-}
-
-// The wash's judgement of a (non-bad) observation at X: depth first, then the
-// residual rule.
-template <int CM>
-__host__ __device__ inline uint8_t tri_judge(const CamPre& cp, const double* in, const double (&X)[3], double u0,
-                                             double u1, const TriRule& R, double& r0, double& r1) {
-    double P[3];
-    tri_project<CM>(cp, in, X, u0, u1, P, r0, r1);
-    const bool front = CM == SFM_CAM_SNAVELY ? P[2] < 0.0 : P[2] > 0.0;
-    if (!(tri_finite(r0) && tri_finite(r1)) || (R.cheirality != 0 && !front)) return kTriDepth;
-    if (R.max_residual_px > 0.0 && sqrt(r0 * r0 + r1 * r1) > R.max_residual_px) return kTriResidual;
-    return kTriKeep;
+    return track_finite(X[0]) && track_finite(X[1]) && track_finite(X[2]);
 }
 
 // A hypothesis' score: more inliers, then the smaller sum of their squared
@@ -284,6 +216,93 @@ __host__ __device__ inline void tri_unrank(int32_t n, ImgOf img, int64_t rank, i
 __host__ __device__ inline int64_t tri_hyp_rank(int64_t h, int64_t npairs, int64_t max_hyp) {
     if (npairs <= max_hyp) return h;
     return h * (npairs / max_hyp) + h * (npairs % max_hyp) / max_hyp;
+}
+
+// One track of n observations by the Lanes::W lanes that share it (every one
+// of them calls it; a group without a point has n = 0).  Lanes supplies this
+// lane's index g, sum(v) over the lanes and best(score, X), the reduction to
+// the best hypothesis by tri_better's total order; on the host W = 1 and
+// both are identities.  The caller's storage is behind accessors over the
+// track's observation index i:
+//   good(i)                 the observation has a bearing
+//   add_gram(G, i)          G += its Gram
+//   judge(i, X, r0, r1)     its reject code and residual at X (judge_obs)
+//   img_of(i)               its image, -1 when not good
+//   out(i, code, r0, r1)    its final code and residual, one lane each
+// Returns what the solve left and, for kTriSolved, X (the same in every lane).
+// LINEAR: M = the good observations' Grams summed in observation order, one
+// solve.  ROBUST: a lane per two-view hypothesis (the solve of two Grams,
+// scored on every good observation in order), the best of them, then the
+// N-view refit over its inliers.
+template <bool ROBUST, class Lanes, class Good, class AddGram, class Judge, class ImgOf, class Out>
+__host__ __device__ inline uint8_t tri_solve_track(const Lanes& L, int32_t n, int32_t max_hyp, Good good,
+                                                   AddGram add_gram, Judge judge, ImgOf img_of, Out out,
+                                                   double (&X)[3]) {
+    constexpr int W = Lanes::W;
+    const int g = L.g;
+    int32_t m_loc = 0;
+    for (int32_t i = g; i < n; i += W) m_loc += good(i);
+    const int32_t m = L.sum(m_loc);
+    uint8_t fin = kTriNoSolve;
+    X[0] = X[1] = X[2] = 0.0;
+    if constexpr (!ROBUST) {
+        if (m >= 2) {
+            double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            for (int32_t i = 0; i < n; ++i)
+                if (good(i)) add_gram(G, i);
+            fin = tri_solve4(G, X) ? kTriSolved : kTriInfinite;
+        }
+    } else {
+        long long np_loc = 0;
+        if (m >= 2)
+            for (int32_t a = g; a < n; a += W) np_loc += tri_row_pairs(n, a, img_of);
+        const long long npairs = L.sum(np_loc);
+        const long long H = npairs < max_hyp ? npairs : (long long)max_hyp;
+        TriScore best{-1, 0.0, 0};
+        double bX[3] = {0.0, 0.0, 0.0};
+        for (long long h = g; h < H; h += W) {
+            int32_t a, b;
+            tri_unrank(n, img_of, tri_hyp_rank(h, npairs, max_hyp), a, b);
+            double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, Xh[3] = {0.0, 0.0, 0.0};
+            add_gram(G, a);
+            add_gram(G, b);
+            TriScore sc{0, 0.0, (int32_t)h};
+            if (tri_solve4(G, Xh)) {
+                for (int32_t i = 0; i < n; ++i) {
+                    if (!good(i)) continue;
+                    double r0, r1;
+                    if (judge(i, Xh, r0, r1) == kObsKeep) {
+                        ++sc.cnt;
+                        sc.ssq += r0 * r0 + r1 * r1;
+                    }
+                }
+            }
+            if (tri_better(sc, best)) {
+                best = sc;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) bX[j] = Xh[j];
+            }
+        }
+        L.best(best, bX);
+        if (best.cnt >= 2) {   // the refit over the winner's inliers (the same in every lane)
+            double G[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            for (int32_t i = 0; i < n; ++i) {
+                if (!good(i)) continue;
+                double r0, r1;
+                if (judge(i, bX, r0, r1) == kObsKeep) add_gram(G, i);
+            }
+            fin = tri_solve4(G, X) ? kTriSolved : kTriInfinite;
+        }
+    }
+    // the final judgement, a lane per observation
+    const double nan = __builtin_nan("");
+    for (int32_t i = g; i < n; i += W) {
+        uint8_t cd = kObsBad;
+        double r0 = nan, r1 = nan;
+        if (good(i)) cd = fin == kTriSolved ? judge(i, X, r0, r1) : (uint8_t)kObsNoPoint;
+        out(i, cd, r0, r1);
+    }
+    return fin;
 }
 
 }  // namespace
