@@ -156,6 +156,16 @@ class TriStats(C.Structure):
                 ("n_obs_depth", C.c_int64), ("n_obs_residual", C.c_int64)]
 
 
+class TracksOpts(C.Structure):
+    _fields_ = [("min_track_len", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class TracksStats(C.Structure):
+    _fields_ = [("n_nodes", C.c_int64), ("n_edges", C.c_int64), ("n_components", C.c_int64),
+                ("n_conflict", C.c_int64), ("n_short", C.c_int64), ("n_tracks", C.c_int64),
+                ("n_obs", C.c_int64), ("max_track_len", C.c_int64)]
+
+
 class SynthBAConfig(C.Structure):
     _fields_ = [("n_cam", C.c_int32), ("k", C.c_int32), ("vis_mode", C.c_int32),
                 ("n_intr", C.c_int32), ("n_pt", C.c_int64), ("seed", C.c_uint64),
@@ -280,6 +290,16 @@ SIGNATURES = [
                                   f64p, u8p, u8p, f64p, C.POINTER(TriStats)]),
     ("sfm_triangulate_host", C.c_int, [C.POINTER(BAProblem), f64p, f64p, C.POINTER(TriOpts),
                                        f64p, u8p, u8p, f64p, C.POINTER(TriStats)]),
+    ("sfm_tracks_default_options", None, [C.POINTER(TracksOpts)]),
+    ("sfm_tracks_build", C.c_int, [C.c_void_p, C.c_int32, i64p, C.c_int64, i32p, i64p, u32p, u32p, f64p,
+                                   C.POINTER(TracksOpts), C.POINTER(C.c_void_p)]),
+    ("sfm_tracks_build_host", C.c_int, [C.c_int32, i64p, C.c_int64, i32p, i64p, u32p, u32p, f64p,
+                                        C.POINTER(TracksOpts), C.POINTER(C.c_void_p)]),
+    ("sfm_tracks_get_stats", C.c_int, [C.c_void_p, C.POINTER(TracksStats)]),
+    ("sfm_tracks_fetch", C.c_int, [C.c_void_p, i64p, i32p, u32p, f64p]),
+    ("sfm_tracks_destroy", C.c_int, [C.c_void_p]),
+    ("sfm_sparse_tracks", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(TracksOpts),
+                                    C.POINTER(C.c_void_p)]),
     ("sfm_ba_intr_width", C.c_int, [C.c_int32]),
     ("sfm_ba_partition", C.c_int, [C.POINTER(BAProblem), C.c_int32, i64p, i64p]),
     ("sfm_ba_describe", C.c_int, [C.POINTER(BAProblem), C.c_int32, C.c_int32, C.POINTER(BAPlanShape)]),

@@ -452,6 +452,139 @@ def triangulate(ctx, problem, extr, intr, opts=None):
                 stats={f: getattr(stats, f) for f, _ in abi.TriStats._fields_})
 
 
+def tracks_default_options():
+    o = abi.TracksOpts()
+    abi.load().sfm_tracks_default_options(C.byref(o))
+    return o
+
+
+def _match_arrays(matches):
+    """{(I, J): [n, 2] of (i, j)} in the dict's own order, or (pairs, counts, i, j)
+    arrays in sfm_mvg_save_matches' layout -> those four arrays, contiguous."""
+    if isinstance(matches, dict):
+        keys = list(matches)
+        pairs = np.array(keys, np.int32).reshape(-1, 2)
+        counts = np.array([len(matches[k]) for k in keys], np.int64)
+        ij = np.concatenate([np.asarray(matches[k], np.uint32).reshape(-1, 2) for k in keys]) \
+            if keys else np.zeros((0, 2), np.uint32)
+        i, j = ij[:, 0], ij[:, 1]
+    else:
+        pairs, counts, i, j = matches
+    return (np.ascontiguousarray(pairs, np.int32).reshape(-1, 2), np.ascontiguousarray(counts, np.int64),
+            np.ascontiguousarray(i, np.uint32), np.ascontiguousarray(j, np.uint32))
+
+
+class Tracks:
+    """sfm_tracks: the tracks of a set of pairwise matches, in canonical order
+    (sfm_tracks_build on ctx; ctx None: sfm_tracks_build_host, on the CPU).
+    feat_off[n_img + 1]: image I owns the node ids feat_off[I] .. feat_off[I+1]-1;
+    matches: {(I, J): [n, 2] of (i, j)} or (pairs, counts, i, j) arrays; xy
+    (optional): [feat_off[n_img], 2] positions, gathered into obs_uv."""
+
+    def __init__(self, ctx, n_img, feat_off, matches, xy=None, opts=None):
+        self.lib = abi.load()
+        self.n_img = int(n_img)
+        off = np.ascontiguousarray(feat_off, np.int64)
+        if len(off) != self.n_img + 1:
+            raise ValueError("Tracks: feat_off must have n_img + 1 entries")
+        pairs, counts, i, j = _match_arrays(matches)
+        # (the library rejects a negative count or 2^31 matches before it reads a match)
+        total = int(counts.sum()) if len(counts) and (counts >= 0).all() else 0
+        if len(counts) != len(pairs) or len(i) != len(j) or (total < 2**31 and len(i) < total):
+            raise ValueError("Tracks: match arrays do not agree in size")
+        if xy is not None:
+            xy = np.ascontiguousarray(xy, np.float64).reshape(-1)
+            if len(xy) < 2 * max(int(off[-1]), 0):
+                raise ValueError("Tracks: xy needs a position per node id")
+            if len(xy) == 0:
+                xy = np.zeros(2)
+        h = C.c_void_p()
+        args = (self.n_img, abi.ptr(off, abi.i64p), len(pairs), abi.ptr(pairs, abi.i32p), abi.ptr(counts, abi.i64p),
+                abi.ptr(i, abi.u32p), abi.ptr(j, abi.u32p), abi.ptr(xy, abi.f64p),
+                C.byref(opts) if opts is not None else None, C.byref(h))
+        if ctx is None:
+            _check(self.lib.sfm_tracks_build_host(*args), "sfm_tracks_build_host")
+        else:
+            _check(self.lib.sfm_tracks_build(ctx.h, *args), "sfm_tracks_build")
+        self._own(h, ctx)
+
+    def _own(self, h, ctx):
+        self.h = h
+        if ctx is not None:
+            ctx._adopt(self)
+
+    @classmethod
+    def _from_handle(cls, h, ctx, n_img):
+        t = cls.__new__(cls)
+        t.lib = abi.load()
+        t.n_img = n_img
+        t._own(h, ctx)
+        return t
+
+    def stats(self):
+        st = abi.TracksStats()
+        _check(self.lib.sfm_tracks_get_stats(self.h, C.byref(st)), "sfm_tracks_get_stats")
+        return {f: getattr(st, f) for f, _ in abi.TracksStats._fields_}
+
+    def fetch(self, uv=True):
+        """dict(pt_offsets [n_tracks + 1], obs_img, obs_feat [n_obs], obs_uv
+        [n_obs, 2]); uv False leaves obs_uv out (tracks built without xy have
+        none: asking is an error)."""
+        st = self.stats()
+        n_trk, n_obs = st["n_tracks"], st["n_obs"]
+        off = np.zeros(n_trk + 1, np.int64)
+        img = np.zeros(max(n_obs, 1), np.int32)
+        feat = np.zeros(max(n_obs, 1), np.uint32)
+        xy = np.zeros(2 * max(n_obs, 1)) if uv else None
+        _check(self.lib.sfm_tracks_fetch(self.h, abi.ptr(off, abi.i64p), abi.ptr(img, abi.i32p),
+                                         abi.ptr(feat, abi.u32p), abi.ptr(xy, abi.f64p)), "sfm_tracks_fetch")
+        return dict(pt_offsets=off, obs_img=img[:n_obs], obs_feat=feat[:n_obs],
+                    obs_uv=xy[:2 * n_obs].reshape(-1, 2) if uv else None)
+
+    def problem(self, img_intr, camera_model=abi.SFM_CAM_PINHOLE):
+        """The tracks as a BAProblem (what triangulate, ba_solve and ba_wash
+        take): img_intr[n_img] maps every image to its intrinsics block.  The
+        problem keeps its arrays alive; no image is held constant."""
+        f = self.fetch()
+        ii = np.ascontiguousarray(img_intr, np.int32)
+        if len(ii) != self.n_img:
+            raise ValueError("Tracks.problem: img_intr must have n_img entries")
+        off = f["pt_offsets"]
+        img = np.ascontiguousarray(f["obs_img"]) if len(f["obs_img"]) else np.zeros(1, np.int32)
+        uv = np.ascontiguousarray(f["obs_uv"].reshape(-1)) if len(f["obs_uv"]) else np.zeros(2)
+        pr = abi.BAProblem()
+        pr.n_img, pr.n_intr = self.n_img, int(ii.max()) + 1 if len(ii) else 0
+        pr.n_pt, pr.n_obs = len(off) - 1, int(off[-1])
+        pr.pt_offsets = abi.ptr(off, abi.i64p)
+        pr.obs_img = abi.ptr(img, abi.i32p)
+        pr.obs_uv = abi.ptr(uv, abi.f64p)
+        pr.img_intr = abi.ptr(ii, abi.i32p)
+        pr.const_img, pr.camera_model, pr.huber_a = -1, camera_model, 0.0
+        pr._keep = (off, img, uv, ii)
+        return pr
+
+    def close(self):
+        if self.h:
+            self.lib.sfm_tracks_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sparse_tracks(ctx, matches_dir, matches_file=None, opts=None):
+    """sfm_sparse_tracks: the Tracks of <matches_dir>/matches.f.bin (or
+    matches_file) over the views of its sfm_data.json and their <stem>.feat."""
+    h = C.c_void_p()
+    _check(ctx.lib.sfm_sparse_tracks(ctx.h, _b(matches_dir), _b(matches_file) if matches_file else None,
+                                     C.byref(opts) if opts is not None else None, C.byref(h)),
+           "sfm_sparse_tracks")
+    return Tracks._from_handle(h, ctx, len(mvg_load_views(str(matches_dir).rstrip("/") + "/sfm_data.json")))
+
+
 def ba_cache_stats(ctx):
     """(reused, grown, fresh) plan counts of sfm_ba_solve on this context."""
     r, g, f = C.c_int64(), C.c_int64(), C.c_int64()

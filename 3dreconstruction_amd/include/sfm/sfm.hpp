@@ -6,6 +6,9 @@
 //   LocalFrame/GlobalFrame src/frame/LocalFrame.h:19-83, GlobalFrame.h:15-160
 //   Triangulator          every world point from its track and the current
 //                         poses (triangulator.hpp; sfm_triangulate)
+//   TracksBuilder         OpenMVG's tracks::TracksBuilder, the first step of the
+//                         engine reconstruction() runs (sparseBuilder.cpp:1474-1508):
+//                         pairwise matches into tracks (tracks.hpp; sfm_tracks_build)
 //   sparse::sparseBuilder src/sparseBuilder/sparseBuilder.h:14-39 — matchPair()
 //                         (exhaustive pairs, .cpp:758-807) and match()
 //                         (Matcher_Regions(0.8, BRUTE_FORCE_L2), .cpp:809-1023)
@@ -30,6 +33,7 @@
 #include "actuator.hpp"
 #include "adjuster.hpp"
 #include "frames.hpp"
+#include "tracks.hpp"
 #include "triangulator.hpp"
 #include "world.hpp"
 
@@ -137,6 +141,24 @@ class Triangulator : public BasicTriangulator<GpuTriBackend> {
    public:
     explicit Triangulator(Context& ctx = Context::thread_default())
         : BasicTriangulator<GpuTriBackend>(GpuTriBackend{&ctx}) {}
+};
+
+// ---------------------------------------------------------------------------
+// TracksBuilder (tracks.hpp) on the GPU: sfm_tracks_build
+// ---------------------------------------------------------------------------
+struct GpuTracksBackend {
+    Context* ctx;
+    int build(int32_t n_img, const int64_t* feat_off, int64_t n_pairs, const int32_t* pairs, const int64_t* counts,
+              const uint32_t* i, const uint32_t* j, const sfm_tracks_opts& o, sfm_tracks** out) const {
+        return sfm_tracks_build(ctx->get(), n_img, feat_off, n_pairs, pairs, counts, i, j, nullptr, &o, out);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+class TracksBuilder : public BasicTracksBuilder<GpuTracksBackend> {
+   public:
+    explicit TracksBuilder(Context& ctx = Context::thread_default())
+        : BasicTracksBuilder<GpuTracksBackend>(GpuTracksBackend{&ctx}) {}
 };
 
 // ---------------------------------------------------------------------------

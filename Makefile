@@ -11,7 +11,7 @@ OBJS := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/*.hpp)
 
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
-     tests/cpp/triangulate_host_test
+     tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -54,3 +54,12 @@ tests/cpp/triangulate_test: tests/cpp/triangulate_test.cpp $(wildcard $(PKG)/inc
 
 tests/cpp/triangulate_host_test: tests/cpp/triangulate_test.cpp $(CSRC)/tri.cpp $(HDRS)
 	g++ -O2 -std=c++17 -w -DTRI_STANDALONE -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $<
+
+# sfm::TracksBuilder: csrc/tracks.cpp's host path compiled in (no library, no
+# HIP runtime: host only), and the same file over the product (--gpu: the GPU façade)
+tests/cpp/tracks_test: tests/cpp/tracks_test.cpp $(CSRC)/tracks.cpp $(HDRS)
+	g++ -O2 -std=c++17 -Wall -DTRACKS_STANDALONE -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $<
+
+tests/cpp/tracks_facade_test: tests/cpp/tracks_test.cpp $(wildcard $(PKG)/include/sfm/*.hpp) $(LIB)
+	g++ -O2 -std=c++17 -Wall -o $@ $< -I/opt/rocm/include -L3dreconstruction_amd/lib -lsfmcore \
+	    -Wl,-rpath,'$$ORIGIN/../../3dreconstruction_amd/lib'

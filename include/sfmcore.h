@@ -95,7 +95,7 @@ typedef struct sfm_ctx_opts {
  * every rank of a sharded solve then returns SFM_ERR_DEVICE together instead
  * of the others waiting in the next collective. */
 #define SFM_CTX_DIAG_FAIL_SOLVE_WAIT 4
-/* Measurement: sfm_fmatrix_ac and sfm_triangulate bracket their kernels with
+/* Measurement: sfm_fmatrix_ac, sfm_triangulate and sfm_tracks_build bracket their kernels with
  * HIP events (after draining the uploads) so that sfm_ctx_last_kernel_ms can
  * report the kernels alone.  Off by default: the extra stream synchronisation and event pair are
  * not part of the filter's production path. */
@@ -683,7 +683,8 @@ int sfm_fmatrix_ac(sfm_ctx* ctx, int64_t n_pairs, const int64_t* off, const doub
                    sfm_fmatrix_result* results, int32_t* inliers);
 
 /* Device time (HIP events on the context's stream) of the kernel(s) of the
- * context's last sfm_fmatrix_ac or sfm_triangulate call, without its host
+ * context's last sfm_fmatrix_ac, sfm_triangulate or sfm_tracks_build (also
+ * through sfm_sparse_tracks) call, without its host
  * normalisation, uploads and downloads (measurement; no reference counterpart).  Only a
  * context created with SFM_CTX_TIME_KERNELS times it; -1 otherwise. */
 int sfm_ctx_last_kernel_ms(sfm_ctx* ctx, double* ms);
@@ -863,6 +864,77 @@ int sfm_triangulate(sfm_ctx* ctx, const sfm_ba_problem* prob, const double* extr
 int sfm_triangulate_host(const sfm_ba_problem* prob, const double* extr, const double* intr,
                          const sfm_tri_opts* opts, double* X, uint8_t* status, uint8_t* keep_obs,
                          double* residual, sfm_tri_stats* stats);
+
+/* ------------------------------------------------------------------------ */
+/* Track building                                                            */
+/* Pairwise feature matches (matches.f.bin, what sfm_sparse_filter writes)   */
+/* into tracks: the first step of OpenMVG's reconstruction engines, which    */
+/* reconstruction() runs on matches.f.bin (sparseBuilder.cpp:1435,           */
+/* :1474-1508): tracks::TracksBuilder Build + Filter + ExportToSTL.          */
+/* Restated from its published code, parity unpinned.         */
+/*                                                                          */
+/* A node is (image, feature); only nodes named by a match exist.  An edge   */
+/* is one match (I, i) - (J, j); a component is a connected component.  A    */
+/* component is removed by the first rule that applies:                      */
+/*   conflict  two of its nodes are different features of one image;         */
+/*   short     it has fewer than min_track_len nodes.                        */
+/* What remains are the tracks, in a canonical order (OpenMVG's track ids    */
+/* are union-find roots and depend on its implementation): tracks by their   */
+/* smallest node (image, then feature), observations inside a track by       */
+/* image.  The set of tracks and each track's map<image, feature> order are  */
+/* OpenMVG's STLMAPTracks.  The tracks are a function of the set of edges:   */
+/* pair order, match order, repeated matches and a pair given as (J, I)      */
+/* change nothing (of the stats, n_edges alone counts the matches as given,  */
+/* repeats included).                                                        */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_tracks sfm_tracks;
+typedef struct sfm_tracks_opts {
+    int32_t min_track_len;    /* 2 (>= 2)                                         */
+    int32_t reserved[3];
+} sfm_tracks_opts;
+typedef struct sfm_tracks_stats {
+    int64_t n_nodes, n_edges, n_components;   /* n_edges: the matches given        */
+    int64_t n_conflict, n_short;              /* removed components, by rule       */
+    int64_t n_tracks, n_obs, max_track_len;   /* what is kept                      */
+} sfm_tracks_stats;
+/* [cpu] {2}; NULL opts below select it. */
+void sfm_tracks_default_options(sfm_tracks_opts* opts);
+/* Image I has features feat_off[I] .. feat_off[I+1]-1 as dense node ids
+ * (feat_off[0] >= 0, non-decreasing; an image may have none).  pairs, counts,
+ * i, j: sfm_mvg_save_matches' layout (pair q = images pairs[2q], pairs[2q+1],
+ * its counts[q] matches consecutive in i / j).  xy (optional): a position per
+ * node id, which sfm_tracks_fetch gathers into obs_uv.  Every argument check
+ * runs on the host before any device call: I == J, an image outside
+ * [0, n_img), a feature index at or past its image's count, a decreasing
+ * feat_off, min_track_len < 2: SFM_ERR_INVALID_ARG; feat_off[n_img] or the
+ * number of matches above 2^31 - 1: SFM_ERR_UNSUPPORTED.  No matches give zero
+ * tracks.  It does not shard.  A context created with SFM_CTX_TIME_KERNELS
+ * reports the kernels' device time through sfm_ctx_last_kernel_ms. */
+int sfm_tracks_build(sfm_ctx* ctx, int32_t n_img, const int64_t* feat_off /* [n_img+1] */,
+                     int64_t n_pairs, const int32_t* pairs /* [2*n_pairs] */, const int64_t* counts,
+                     const uint32_t* i, const uint32_t* j, const double* xy /* [2*feat_off[n_img]] or NULL */,
+                     const sfm_tracks_opts* opts, sfm_tracks** out);
+/* [cpu] The same from a serial union-find on the host: the same outputs bit
+ * for bit (everything is integral, obs_uv is a gather). */
+int sfm_tracks_build_host(int32_t n_img, const int64_t* feat_off, int64_t n_pairs, const int32_t* pairs,
+                          const int64_t* counts, const uint32_t* i, const uint32_t* j, const double* xy,
+                          const sfm_tracks_opts* opts, sfm_tracks** out);
+/* [cpu] */
+int sfm_tracks_get_stats(sfm_tracks* t, sfm_tracks_stats* stats);
+/* [cpu] The tracks as a sfm_ba_problem takes them: pt_offsets[n_tracks+1]
+ * (pt_offsets = {0} without tracks), obs_img[n_obs], obs_feat[n_obs] (the
+ * feature's index in its image), obs_uv[2*n_obs]; any may be NULL.  obs_uv of
+ * a handle built without xy is SFM_ERR_INVALID_ARG. */
+int sfm_tracks_fetch(sfm_tracks* t, int64_t* pt_offsets, int32_t* obs_img, uint32_t* obs_feat,
+                     double* obs_uv);
+/* [cpu] */
+int sfm_tracks_destroy(sfm_tracks* t);
+/* File-staged: the views of <matches_dir>/sfm_data.json (image I = the I-th
+ * view by id_view), every <stem>.feat (the feature counts, and x y as xy) and
+ * <matches_dir>/<matches_file> (NULL: matches.f.bin), then sfm_tracks_build.
+ * A match naming a view that sfm_data.json lacks is SFM_ERR_INVALID_ARG. */
+int sfm_sparse_tracks(sfm_ctx* ctx, const char* matches_dir, const char* matches_file,
+                      const sfm_tracks_opts* opts, sfm_tracks** out);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
