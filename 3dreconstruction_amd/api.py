@@ -87,32 +87,33 @@ def comm_unique_id():
     return bytes(buf)
 
 
-def match_dense(ctx, a, b, mode=abi.SFM_MATCH_RATIO, ratio=0.8):
-    a = np.ascontiguousarray(a, np.uint8).reshape(-1, 128)
-    b = np.ascontiguousarray(b, np.uint8).reshape(-1, 128)
+# descriptor dtype -> (C suffix, descriptor pointer, distance dtype, distance pointer)
+_MATCH_KINDS = {np.uint8: ("", abi.u8p, np.int32, abi.i32p),
+                np.float32: ("_f32", abi.f32p, np.float32, abi.f32p)}
+
+
+def _match_dense(ctx, a, b, mode, ratio, dtype):
+    sfx, dp, dist, distp = _MATCH_KINDS[dtype]
+    a = np.ascontiguousarray(a, dtype).reshape(-1, 128)
+    b = np.ascontiguousarray(b, dtype).reshape(-1, 128)
     n_out = len(a) if mode == abi.SFM_MATCH_MUTUAL else len(b)
     idx = np.zeros(max(n_out, 1), np.int32)
-    d2 = np.zeros(max(n_out, 1), np.int32)
+    d2 = np.zeros(max(n_out, 1), dist)
     o = abi.MatchOptions(mode, ratio)
-    _check(ctx.lib.sfm_match_dense(ctx.h, abi.ptr(a, abi.u8p), len(a), abi.ptr(b, abi.u8p), len(b),
-                                   C.byref(o), abi.ptr(idx, abi.i32p), abi.ptr(d2, abi.i32p)),
-           "sfm_match_dense")
+    name = "sfm_match_dense" + sfx
+    _check(getattr(ctx.lib, name)(ctx.h, abi.ptr(a, dp), len(a), abi.ptr(b, dp), len(b), C.byref(o),
+                                  abi.ptr(idx, abi.i32p), abi.ptr(d2, distp)), name)
     return idx[:n_out], d2[:n_out]
+
+
+def match_dense(ctx, a, b, mode=abi.SFM_MATCH_RATIO, ratio=0.8):
+    return _match_dense(ctx, a, b, mode, ratio, np.uint8)
 
 
 def match_dense_f32(ctx, a, b, mode=abi.SFM_MATCH_RATIO, ratio=0.8):
     """sfm_match_dense_f32: float descriptors (cv::Mat CV_32F); returns
     (idx, squared distance as float32, -1 where unmatched)."""
-    a = np.ascontiguousarray(a, np.float32).reshape(-1, 128)
-    b = np.ascontiguousarray(b, np.float32).reshape(-1, 128)
-    n_out = len(a) if mode == abi.SFM_MATCH_MUTUAL else len(b)
-    idx = np.zeros(max(n_out, 1), np.int32)
-    d2 = np.zeros(max(n_out, 1), np.float32)
-    o = abi.MatchOptions(mode, ratio)
-    _check(ctx.lib.sfm_match_dense_f32(ctx.h, abi.ptr(a, abi.f32p), len(a), abi.ptr(b, abi.f32p), len(b),
-                                       C.byref(o), abi.ptr(idx, abi.i32p), abi.ptr(d2, abi.f32p)),
-           "sfm_match_dense_f32")
-    return idx[:n_out], d2[:n_out]
+    return _match_dense(ctx, a, b, mode, ratio, np.float32)
 
 
 class MatchPlan:
@@ -122,19 +123,14 @@ class MatchPlan:
     def __init__(self, ctx, desc, offsets):
         self.ctx = ctx
         self.f32 = np.asarray(desc).dtype == np.float32
+        self._sfx, dp, self._dist, self._distp = _MATCH_KINDS[np.float32 if self.f32 else np.uint8]
+        desc = np.ascontiguousarray(desc, np.float32 if self.f32 else np.uint8).reshape(-1, 128)
         offsets = np.ascontiguousarray(offsets, np.int64)
         self.n_img = len(offsets) - 1
         h = C.c_void_p()
-        if self.f32:
-            desc = np.ascontiguousarray(desc, np.float32).reshape(-1, 128)
-            _check(ctx.lib.sfm_match_plan_create_f32(ctx.h, abi.ptr(desc, abi.f32p),
-                                                     abi.ptr(offsets, abi.i64p), self.n_img, C.byref(h)),
-                   "sfm_match_plan_create_f32")
-        else:
-            desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 128)
-            _check(ctx.lib.sfm_match_plan_create(ctx.h, abi.ptr(desc, abi.u8p),
-                                                 abi.ptr(offsets, abi.i64p), self.n_img, C.byref(h)),
-                   "sfm_match_plan_create")
+        name = "sfm_match_plan_create" + self._sfx
+        _check(getattr(ctx.lib, name)(ctx.h, abi.ptr(desc, dp), abi.ptr(offsets, abi.i64p), self.n_img,
+                                      C.byref(h)), name)
         self.h = h
         self.n_pairs = 0
         ctx._adopt(self)
@@ -150,23 +146,17 @@ class MatchPlan:
         return tot.value if count else None
 
     def fetch(self):
+        name = "sfm_match_plan_fetch" + self._sfx
+        fetch = getattr(self.ctx.lib, name)
         counts = np.zeros(max(self.n_pairs, 1), np.int64)
-        fetch = self.ctx.lib.sfm_match_plan_fetch_f32 if self.f32 else self.ctx.lib.sfm_match_plan_fetch
-        _check(fetch(self.h, abi.ptr(counts, abi.i64p), None, None, None), "sfm_match_plan_fetch")
+        _check(fetch(self.h, abi.ptr(counts, abi.i64p), None, None, None), name)
         counts = counts[:self.n_pairs]
         tot = int(counts.sum())
         i = np.zeros(max(tot, 1), np.uint32)
         j = np.zeros(max(tot, 1), np.uint32)
-        if self.f32:
-            d = np.zeros(max(tot, 1), np.float32)
-            _check(self.ctx.lib.sfm_match_plan_fetch_f32(self.h, abi.ptr(counts, abi.i64p),
-                                                         abi.ptr(i, abi.u32p), abi.ptr(j, abi.u32p),
-                                                         abi.ptr(d, abi.f32p)), "sfm_match_plan_fetch_f32")
-        else:
-            d = np.zeros(max(tot, 1), np.int32)
-            _check(self.ctx.lib.sfm_match_plan_fetch(self.h, abi.ptr(counts, abi.i64p),
-                                                     abi.ptr(i, abi.u32p), abi.ptr(j, abi.u32p),
-                                                     abi.ptr(d, abi.i32p)), "sfm_match_plan_fetch")
+        d = np.zeros(max(tot, 1), self._dist)
+        _check(fetch(self.h, abi.ptr(counts, abi.i64p), abi.ptr(i, abi.u32p), abi.ptr(j, abi.u32p),
+                     abi.ptr(d, self._distp)), name)
         return counts, i[:tot], j[:tot], d[:tot]
 
     def cascade_index(self, pairs):
@@ -201,7 +191,7 @@ class MatchPlan:
 
 
 def _mix64(z):
-    z = np.uint64(z)
+    z = np.asarray(z, np.uint64)
     with np.errstate(over="ignore"):
         z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
@@ -210,17 +200,16 @@ def _mix64(z):
 
 def match_digest(counts, i, j, d):
     """Host restatement of the device digest (order-independent)."""
-    tot = np.uint64(0)
-    off = 0
+    counts = np.asarray(counts, np.int64)
+    n = int(counts.sum())
+    key = (np.asarray(i[:n], np.uint64) << np.uint64(32)) | np.asarray(j[:n], np.uint64)
+    m = _mix64(key ^ (np.asarray(d[:n]).astype(np.uint32).astype(np.uint64) << np.uint64(21)))
+    # per-pair sums modulo 2^64 (an empty pair sums to 0)
+    h = np.zeros(len(counts), np.uint64)
+    np.add.at(h, np.repeat(np.arange(len(counts)), counts), m)
     with np.errstate(over="ignore"):
-        for p, c in enumerate(counts):
-            h = np.uint64(0)
-            for k in range(off, off + int(c)):
-                key = (np.uint64(i[k]) << np.uint64(32)) | np.uint64(j[k])
-                h = h + _mix64(key ^ (np.uint64(np.uint32(d[k])) << np.uint64(21)))
-            off += int(c)
-            tot = tot + _mix64(h + np.uint64(0x9E3779B97F4A7C15) * np.uint64(p + 1))
-    return int(tot)
+        pair_id = np.arange(1, len(counts) + 1, dtype=np.uint64)
+        return int(_mix64(h + np.uint64(0x9E3779B97F4A7C15) * pair_id).sum(dtype=np.uint64))
 
 
 def exhaustive_pairs(n):
