@@ -291,17 +291,71 @@ struct BandArrow {
         for (size_t k = 0; k < corner.size(); ++k) corner[k] += o.corner[k];
     }
     // In-place Cholesky L L' = S.  Returns false if not positive definite.
-    bool cholesky() {
-        for (int64_t i = 0; i < nb; ++i) {
-            for (int64_t j = std::max<int64_t>(0, i - bw); j <= i; ++j) {
-                double s = band[i * (bw + 1) + (i - j)];
-                for (int64_t k = std::max<int64_t>(0, i - bw); k < j; ++k)
-                    s -= band[i * (bw + 1) + (i - k)] * band[j * (bw + 1) + (j - k)];
-                if (i == j) {
-                    if (!(s > 0.0)) return false;
-                    band[i * (bw + 1)] = std::sqrt(s);
-                } else {
-                    band[i * (bw + 1) + (i - j)] = s / band[j * (bw + 1)];
+    // L_ij = (S_ij - sum_k L_ik L_jk) / L_jj with k ascending from the band's
+    // start of row i, for every element; the band goes by panels of kPanel
+    // columns: the panel's own rows first (serial), then every row below it
+    // (independent of each other: `threads` of them at a time), the panel's
+    // sums of one row advancing together over the columns before the panel.
+    // Each element's sum keeps its order, so the factor does not depend on
+    // the panel width or the thread count, bit for bit (a 6400-row dense band
+    // took 48 s in one row-by-row pass).
+    bool cholesky(int threads = 1) {
+        constexpr int64_t kPanel = 16;
+        const int64_t ld = bw + 1;
+        std::vector<double> panel;
+        for (int64_t j0 = 0; j0 < nb; j0 += kPanel) {
+            const int64_t j1 = std::min(nb, j0 + kPanel);
+            for (int64_t i = j0; i < j1; ++i) {
+                const int64_t ks = std::max<int64_t>(0, i - bw);
+                for (int64_t j = std::max(j0, ks); j <= i; ++j) {
+                    double s = band[i * ld + (i - j)];
+                    for (int64_t k = ks; k < j; ++k) s -= band[i * ld + (i - k)] * band[j * ld + (j - k)];
+                    if (i == j) {
+                        if (!(s > 0.0)) return false;
+                        band[i * ld] = std::sqrt(s);
+                    } else {
+                        band[i * ld + (i - j)] = s / band[j * ld];
+                    }
+                }
+            }
+            const int64_t i1 = std::min(nb, j1 + bw);   // rows below the panel that reach it
+            if (i1 <= j1) continue;
+            // the panel's rows, transposed: Pt[k * kPanel + q] = L_{j0+q, k} for k < j0 (0 outside the band)
+            const int64_t k0 = std::max<int64_t>(0, j0 - bw);
+            panel.resize((size_t)nb * kPanel);
+            for (int64_t k = k0; k < j0; ++k)
+                for (int64_t q = 0; q < kPanel; ++q) {
+                    const int64_t j = j0 + q;
+                    panel[k * kPanel + q] = j < j1 && j - k <= bw ? band[j * ld + (j - k)] : 0.0;
+                }
+            const double* Pt = panel.data();
+#pragma omp parallel for schedule(static) num_threads(threads) if (threads > 1 && i1 - j1 > 64)
+            for (int64_t i = j1; i < i1; ++i) {
+                double* Ri = &band[i * ld];
+                const int64_t ks = std::max<int64_t>(0, i - bw), jlo = std::max(j0, ks);
+                double s[kPanel];
+                for (int64_t q = 0; q < kPanel; ++q) s[q] = j0 + q >= jlo && j0 + q < j1 ? Ri[i - (j0 + q)] : 0.0;
+                if (ks < j0) {   // (otherwise the row starts inside the panel)
+                    // two columns per vector lane pair, the accumulators in registers: the same
+                    // multiply and subtract per element (no contraction), k ascending
+                    typedef double v2d __attribute__((vector_size(16), aligned(8)));
+                    v2d acc[kPanel / 2];
+#pragma GCC unroll 8
+                    for (int q = 0; q < kPanel / 2; ++q) acc[q] = v2d{s[2 * q], s[2 * q + 1]};
+                    for (int64_t k = ks; k < j0; ++k) {
+                        const double l = Ri[i - k];
+                        const v2d lv = {l, l};
+                        const v2d* p = reinterpret_cast<const v2d*>(Pt + k * kPanel);
+#pragma GCC unroll 8
+                        for (int q = 0; q < kPanel / 2; ++q) acc[q] -= lv * p[q];
+                    }
+#pragma GCC unroll 8
+                    for (int q = 0; q < kPanel / 2; ++q) { s[2 * q] = acc[q][0]; s[2 * q + 1] = acc[q][1]; }
+                }
+                for (int64_t j = jlo; j < j1; ++j) {
+                    double sj = s[j - j0];
+                    for (int64_t k = jlo; k < j; ++k) sj -= Ri[i - k] * band[j * ld + (j - k)];
+                    Ri[i - j] = sj / band[j * ld];
                 }
             }
         }
@@ -648,7 +702,7 @@ struct Oracle {
             std::copy(buf.begin() + S.size(), buf.end(), rhs.begin());
         }
         for (int64_t c = 0; c < nF; ++c) S.at(c, c) += lmF[c] * lmF[c];
-        if (!S.cholesky()) return false;
+        if (!S.cholesky(nthreads)) return false;
         yF = rhs;
         S.solve(yF);
         // back substitution: yE = Vi (bE - W' yF)

@@ -4,6 +4,14 @@ the full normal equations H y = g over every parameter column, formed densely
 in np.longdouble (64-bit mantissa) and solved to a backward error of 2^-60.
 No Schur complement, no blocks, no bands.
 
+Past DENSE_MAX unknowns H is not formed: the residual g - H y of the same
+certificate comes from the Jacobian rows (Operator, longdouble), and y from
+iterative refinement with an fp64 direct solve of a sparse fp64 copy of H as
+the preconditioner (SchurFactor).  y is accepted by its residual alone,
+however it was found, so the reference still shares no structure with the
+code under test; test_matrix_free_reference_agrees_with_the_dense_one holds
+the two paths against each other on every scene small enough for both.
+
 What is taken from the oracle: the per-observation residual and Jacobian
 (orc_ba_jacobian_model, mode 0 -- pinned to dual numbers and finite
 differences by test_oracle_ba / test_snavely / test_radial3; the fp64 values
@@ -17,6 +25,9 @@ import ctypes as C
 import math
 
 import numpy as np
+import scipy.linalg as sl
+import scipy.sparse as sp
+import scipy.sparse.linalg as spl
 
 import _helpers as H
 
@@ -28,6 +39,7 @@ SKIP_REASON = (f"np.longdouble has a {np.finfo(LD).nmant}-bit mantissa here; the
                "the 64-bit mantissa of the x87 extended format (nmant >= 63)")
 BACKWARD_ERROR_MAX = 2.0 ** -60
 U = 2.0 ** -53
+DENSE_MAX = 2500    # unknowns up to which H is formed densely in longdouble; past it the matrix-free path
 
 
 def pack(params):
@@ -182,9 +194,8 @@ def _solve(Hm, g):
     return y, be, H64
 
 
-def normal_equations(sc, x0, x, radius, opts):
-    """(H, g, J_s rows, f, scale, colnorm^2 of J_s) at x: H = J_s' J_s + clamp(colnorm^2) / radius
-    accumulated observation by observation in longdouble, g = J_s' f."""
+def scaled_rows(sc, x0, x, radius, opts):
+    """(J_s rows, f, scale, colnorm^2 of J_s, clamp(colnorm^2) / radius, g = J_s' f) at x, in longdouble."""
     lay = layout(sc)
     n = lay.n
     lin = linearize(sc, x)
@@ -193,15 +204,113 @@ def normal_equations(sc, x0, x, radius, opts):
     Js = lin["Jc"] * sx[lay.idx][:, None, :]
     f = lin["f"]
     cn = colnorm2(lay, Js)
-    diag = np.clip(cn, LD(opts.min_lm_diagonal), LD(opts.max_lm_diagonal))
+    diag = np.clip(cn, LD(opts.min_lm_diagonal), LD(opts.max_lm_diagonal)) / LD(radius)
+    g = np.zeros(n + 1, LD)
+    np.add.at(g, lay.idx, Js[:, 0, :] * f[:, 0, None] + Js[:, 1, :] * f[:, 1, None])
+    return Js, f, scale, cn, diag, g[:n]
+
+
+def normal_equations(sc, x0, x, radius, opts):
+    """(H, g, J_s rows, f, scale, colnorm^2 of J_s) at x: H = J_s' J_s + clamp(colnorm^2) / radius
+    accumulated observation by observation in longdouble, g = J_s' f."""
+    lay = layout(sc)
+    n = lay.n
+    assert n <= DENSE_MAX
+    Js, f, scale, cn, diag, g = scaled_rows(sc, x0, x, radius, opts)
     Hm = np.zeros((n + 1, n + 1), LD)
     np.add.at(Hm, (lay.idx[:, :, None], lay.idx[:, None, :]),
               Js[:, 0, :, None] * Js[:, 0, None, :] + Js[:, 1, :, None] * Js[:, 1, None, :])
     Hm = Hm[:n, :n]
-    Hm[np.arange(n), np.arange(n)] += diag / LD(radius)
-    g = np.zeros(n + 1, LD)
-    np.add.at(g, lay.idx, Js[:, 0, :] * f[:, 0, None] + Js[:, 1, :] * f[:, 1, None])
-    return Hm, g[:n], Js, f, scale, cn
+    Hm[np.arange(n), np.arange(n)] += diag
+    return Hm, g, Js, f, scale, cn
+
+
+class Operator:
+    """y -> H y = J_s' (J_s y) + (clamp(colnorm^2) / radius) y in longdouble, straight from the Jacobian rows
+    (gather by lay.idx, scatter by np.add.at): H is never formed, so the layout may be of any size.  This is
+    the residual of the certificate.  |H|_inf, the certificate's scale, and the preconditioner come from a
+    sparse fp64 copy of H (J' J of the fp64 rows: every observation couples its own 9 + iw columns only)."""
+
+    def __init__(self, lay, Js, diag):
+        self.lay, self.Js, self.diag, self.n = lay, Js, diag, lay.n
+        self._h64 = None
+
+    def __call__(self, y):
+        lay, Js = self.lay, self.Js
+        s = np.concatenate([y, [LD(0)]])
+        m = (Js * s[lay.idx][:, None, :]).sum(axis=2)
+        out = np.zeros(self.n + 1, LD)
+        np.add.at(out, lay.idx, Js[:, 0, :] * m[:, 0, None] + Js[:, 1, :] * m[:, 1, None])
+        return out[:self.n] + self.diag * y
+
+    def h64(self):
+        """H rounded to fp64 row by row, sparse (CSR)."""
+        if self._h64 is None:
+            n, (no, _, w) = self.n, self.Js.shape
+            rows = np.repeat(np.arange(2 * no), w)
+            cols = np.repeat(self.lay.idx[:, None, :], 2, axis=1).reshape(-1)
+            J = sp.csr_matrix((self.Js.astype(np.float64).reshape(-1), (rows, cols)), shape=(2 * no, n + 1))[:, :n]
+            self._h64 = (J.T @ J + sp.diags(self.diag.astype(np.float64))).tocsr()
+        return self._h64
+
+    def norm_inf(self):
+        return float(abs(self.h64()).sum(axis=1).max())
+
+    def backward_error(self, y, g):
+        """|g - H y|_inf / (|H|_inf |y|_inf + |g|_inf), the residual in longdouble."""
+        return float(np.abs(g - self(y)).max() / (LD(self.norm_inf()) * np.abs(y).max() + np.abs(g).max()))
+
+
+class SchurFactor:
+    """An fp64 direct solve with the sparse fp64 H, used as a preconditioner only: the 3 x 3 point blocks (the
+    trailing n_e columns; the layout puts the points last) eliminated, the reduced system dense, factored by
+    scipy.linalg.cho_factor.  Whatever it returns only speeds the refinement up or slows it down: y is
+    accepted by the longdouble residual alone."""
+
+    def __init__(self, H64, n_e):
+        n = H64.shape[0]
+        nf = n - n_e
+        coo = H64[nf:, nf:].tocoo()
+        assert np.array_equal(coo.row // 3, coo.col // 3), "the point block of H is block diagonal"
+        V = np.zeros((n_e // 3, 3, 3))
+        V[coo.row // 3, coo.row % 3, coo.col % 3] = coo.data
+        k = np.arange(n_e // 3)
+        self.Vi = sp.bsr_matrix((np.linalg.inv(V), k, np.arange(n_e // 3 + 1)), shape=(n_e, n_e)).tocsr()
+        self.W = H64[:nf, nf:].tocsr()
+        S = (H64[:nf, :nf] - self.W @ self.Vi @ self.W.T).toarray()
+        self.cf = sl.cho_factor(S, lower=True, overwrite_a=True, check_finite=False)
+        self.nf = nf
+
+    def __call__(self, r):
+        rf, re = r[:self.nf], r[self.nf:]
+        yf = sl.cho_solve(self.cf, rf - self.W @ (self.Vi @ re), check_finite=False)
+        return np.concatenate([yf, self.Vi @ (re - self.W.T @ yf)])
+
+
+def solve_matrix_free(op, g, n_e):
+    """H y = g for an Operator: SchurFactor as the preconditioner, iterative refinement on longdouble
+    residuals until the normwise backward error is <= 2^-60 (asserted, as _solve does); kappa = lambda_max /
+    lambda_min of the fp64 H by Lanczos (eigsh: the largest directly, the smallest in shift-invert mode
+    about 0 with the factor as the inverse).  Returns (y, backward error, kappa)."""
+    H64 = op.h64()
+    pre = SchurFactor(H64, n_e)
+    hn, gn = LD(op.norm_inf()), np.abs(g).max()
+    y = np.zeros(len(g), LD)
+    be = np.inf
+    for _ in range(12):
+        res = g - op(y)
+        be = float(np.abs(res).max() / (hn * np.abs(y).max() + gn))
+        if be <= BACKWARD_ERROR_MAX / 4:
+            break
+        y = y + pre(res.astype(np.float64)).astype(LD)
+    assert be <= BACKWARD_ERROR_MAX, f"reference solve: backward error 2^{math.log2(be):.1f} > 2^-60"
+    n = len(g)
+    A = spl.LinearOperator((n, n), matvec=lambda v: H64 @ v, dtype=np.float64)
+    v0 = np.ones(n)
+    top = spl.eigsh(A, k=1, which="LA", v0=v0, tol=1e-9, return_eigenvectors=False)[0]
+    low = spl.eigsh(A, k=1, sigma=0.0, which="LM", v0=v0, tol=1e-9, return_eigenvectors=False,
+                    OPinv=spl.LinearOperator((n, n), matvec=pre, dtype=np.float64))[0]
+    return y, be, float(top / low)
 
 
 def gradient_classes(sc, p):
@@ -223,10 +332,14 @@ def lm_step(sc, x0, x, radius, opts, decrease_factor=2.0):
         return _steps[key]
     lay = layout(sc)
     lin = linearize(sc, x)
-    Hm, g, Js, f, scale, _ = normal_equations(sc, x0, x, radius, opts)
-    y, be, H64 = _solve(Hm, g)
-    ev = np.linalg.eigvalsh(H64)    # H is symmetric positive definite: cond_2 = lambda_max / lambda_min
-    cond = float(ev[-1] / ev[0])
+    if lay.n <= DENSE_MAX:
+        Hm, g, Js, f, scale, _ = normal_equations(sc, x0, x, radius, opts)
+        y, be, H64 = _solve(Hm, g)
+        ev = np.linalg.eigvalsh(H64)    # H is symmetric positive definite: cond_2 = lambda_max / lambda_min
+        cond = float(ev[-1] / ev[0])
+    else:
+        Js, f, scale, _, diag, g = scaled_rows(sc, x0, x, radius, opts)
+        y, be, cond = solve_matrix_free(Operator(lay, Js, diag), g, 3 * sc.n_pt)
     s = np.concatenate([-y, [LD(0)]])
     m = (Js * s[lay.idx][:, None, :]).sum(axis=2)               # J_s s per residual row
     model_cost_change = -(m * (f + m / 2)).sum()

@@ -243,10 +243,13 @@ def test_dense_solve_under_contention(chain, split):
     """the dense RCS solved while another context keeps the
     CUs busy -- the condition under which dense_panel_kernel's former store of
     L_kk over A_kk (round 4) corrupted the panels of late
-    workgroups, and under which the dataflow kernels (dense_flow_kernel,
-    dense_back_all_kernel) wait for workgroups that are not resident yet.
-    chain: the launch chain (panel + trailing-update launches); else the
-    dataflow kernels.  split (round 6): a camera band of 13 blocks (14-view
+    workgroups, and under which the dataflow kernel (dense_flow_kernel)
+    waits for workgroups that are not resident yet.  (dense_back_all_kernel
+    does not run here: at 10 and 19 block columns the dataflow kernel does
+    its substitutions; it runs past 100 columns, pinned without load by
+    test_lm_step_gpu's dense_chain_101.)
+    chain: the launch chain (panel + trailing-update launches and the
+    dense_back_kernel loop); else the dataflow kernel.  split (round 6): a camera band of 13 blocks (14-view
     tracks, too wide for the BCR solver), which the dataflow schedule factors
     with two chain workgroups (nested dissection, dense_flow_plan).  Each must
     take the oracle's decisions, with the matcher provably running during the

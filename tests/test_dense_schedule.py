@@ -225,6 +225,29 @@ def test_dense_schedule_random_visibility():
         np.testing.assert_allclose(got, ref, rtol=0, atol=1e-10 * np.abs(ref).max())
 
 
+def test_dense_schedule_at_the_dataflow_limit():
+    """1067 images, one constant: 6 * 1066 + 4 = 6400 rows, 100 block columns, the last size the dataflow
+    solve takes (5247 tasks, sums of up to 99 terms).  Every image is observed, so the plan's camera order is
+    image order (true_matrix's assumption); the replay solves it and never stalls with 254, 3 or 1 workers."""
+    pr = random_problem(1067, 4000)
+    sh, meta = api.ba_dense_schedule(pr)
+    assert sh["flow"] == 1 and sh["chains"] == 1 and sh["nt"] == 100 and sh["nF"] == 6 * 1066 + 4, sh
+    assert sh["tasks"] > 254
+    rng = np.random.default_rng(13)
+    S = true_matrix(pr, sh, rng)
+    rhs = rng.normal(size=S.shape[0])
+    ref = np.linalg.solve(S, rhs)
+    for workers in (254, 3, 1):
+        got = replay(sh, meta, S, rhs, workers)
+        np.testing.assert_allclose(got, ref, rtol=0, atol=1e-10 * np.abs(ref).max())
+
+
+def test_dense_schedule_absent_past_the_dataflow_limit():
+    """One image more: 101 block columns, the launch chain; no dataflow schedule."""
+    sh, meta = api.ba_dense_schedule(random_problem(1068, 4000))
+    assert sh["nt"] == 101 and sh["nF"] == 6 * 1067 + 4 and sh["flow"] == 0 and len(meta) == 0, sh
+
+
 def percam_problem(n_img, max_len, closed, seed=9, pts_per_img=30):
     """RADIAL3 with one intrinsics block per image (reconstruction()'s
     grouping): the intrinsics arrow is as wide as the camera band and itself

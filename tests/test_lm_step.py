@@ -1,7 +1,10 @@
 """CPU: single Levenberg-Marquardt iterations of oracle/ba_oracle.cpp against
-the extended-precision dense reference tests/_lm_reference.py.
+the extended-precision reference tests/_lm_reference.py (H dense in
+longdouble up to 2500 unknowns, matrix-free past that; the same 2^-60
+certificate either way).
 
-For every scene and threads in {1, 2, 3, 8} the oracle runs with
+For every scene and threads in {1, 2, 3, 8} (the three many-tile scenes of
+LARGE: 8 only) the oracle runs with
 max_num_iterations = n (n = 1, 2, 3; all tolerances 0, so it takes exactly n
 iterations).  The reference is fed the oracle's own x_{n-1} (the parameters
 the n-1 run wrote back) and trace[n-1].trust_region_radius, so every
@@ -62,9 +65,37 @@ iterations; kappa and B at the last iteration, where the radius is largest):
   no_gauge            712   0.098       5.1e5     1.1e-10   (exempt from the cap; it meets it all the same)
   clamped             220   3.6e-4      1.8e9     4.0e-7    (radius 1e1)
   rejecting           520   0.027       1.2e7     2.6e-9    (radius 1e7, n = 1..4)
+  dense_flow_wrap       10282   0.039    4.5e5     1.0e-10   (8 threads; matrix-free reference)
+  percam_radial3_band    2250   0.011    3.4e9     7.6e-7    (8 threads)
+  dense_chain_101       24406   0.146    5.5e5     1.2e-10   (8 threads; matrix-free reference)
 
   maximum ratio 0.235 (band_arrow4, 1 thread, n = 1)  ->  8 x = 1.88  ->  C_STEP = 2
   (test_c_step_is_eight_times_the_oracle_worst_ratio regenerates the table and asserts the choice)
+
+The many-tile dense scenes (LARGE) are each the smallest that reaches its
+mechanism in csrc/ba_bcr.hip, asserted through sfm_ba_dense_schedule together
+with the next smaller scene that does not:
+  dense_flow_wrap      214 cameras, random visibility: the dataflow solve on
+                       one chain, 21 block columns, 270 tasks -- more than the
+                       255 workers a 256-CU device can give, so workers take
+                       several tasks in order (213 cameras: 20 columns, 247)
+  percam_radial3_band  47 cameras, RADIAL3, one intrinsics block each: the
+                       Cuthill-McKee tile order split over two chains, an
+                       intrinsics tile among the first nt / 2 (46: one chain)
+  dense_chain_101      1068 cameras: 6406 rows, 101 block columns, past the
+                       dataflow limit: panel / update launches in groups of
+                       four columns, then dense_back_all_kernel (1067: 100
+                       columns, dataflow)
+Their ratios stay below band_arrow4's, so C_STEP = 2 covers them.  CPU cost
+measured on an 8-core x86 host: this module 50 s before the three scenes,
+about 2 min with them (dense_chain_101 runs twice, once more for the C_STEP
+table); dense_chain_101 takes 13 s for its three
+reference steps (4 s each: sparse fp64 H, the 6406-row reduced system's
+factor, two Lanczos runs, 2-3 refinements) and 30 s for the oracle's six
+iterations (5 s each; 48 s each before the oracle's band factor went by
+panels over the threads); dense_flow_wrap 2 s + 1 s, percam_radial3_band
+(dense reference) 6 s + 0.4 s; the dense / matrix-free cross-check of the 18
+older scenes under 1.5 s each.
 
 gradient_max_norm is a maximum over all columns, so one trace entry witnesses
 only the column class that holds the largest |g| entry.  With the generator's
@@ -207,6 +238,51 @@ def _two_chains():
     return sc
 
 
+def _schedule(sc):
+    """The dense dataflow schedule's shape, and whether an intrinsics tile (natural index >= nb / 64) stands
+    among the first nt // 2 positions of its order (test_dense_schedule_banded_arrow's condition)."""
+    sh, meta = api.ba_dense_schedule(sc.problem())
+    nt = sh["nt"]
+    sh["intr_early"] = bool(len(meta)) and any(int(p) >= sh["nb"] // 64 for p in meta[:nt // 2])
+    return sh
+
+
+def _dense_flow_wrap():
+    """Random visibility, the dataflow solve on one chain with more tasks than a 256-CU device has workers
+    (workers = min(tasks, CUs - chains)): every worker takes several tasks in order.  214 cameras are 21
+    block columns and 270 tasks; 213 are 20 columns and 247 tasks."""
+    def wraps(sh):
+        return sh["flow"] == 1 and sh["chains"] == 1 and sh["tasks"] > 256
+    sc = H.Scene(214, 3000, 6, vis_mode=1, outliers=0.2)
+    assert wraps(_schedule(sc)), _schedule(sc)
+    fewer = H.Scene(213, 3000, 6, vis_mode=1, outliers=0.2)
+    assert not wraps(_schedule(fewer)), _schedule(fewer)
+    return sc
+
+
+def _percam_radial3_band():
+    """RADIAL3 with one intrinsics block per camera on an open orbit: 47 cameras is the smallest count for
+    which the tiles take the Cuthill-McKee order and split over two chains (46: image order, one chain)."""
+    def banded(sh):
+        return sh["flow"] == 1 and sh["chains"] == 2 and sh["intr_early"]
+    sc = H.Scene(47, 564, 4, n_intr=47, model=abi.SFM_CAM_RADIAL3, outliers=0.2)
+    assert banded(_schedule(sc)), _schedule(sc)
+    fewer = H.Scene(46, 552, 4, n_intr=46, model=abi.SFM_CAM_RADIAL3, outliers=0.2)
+    assert not banded(_schedule(fewer)), _schedule(fewer)
+    return sc
+
+
+def _dense_chain_101():
+    """1068 cameras, one of them constant: 6 * 1067 + 4 = 6406 rows, 101 block columns, one past the
+    dataflow solve's limit: the panel / update launch chain and the all-resident back substitution."""
+    sc = H.Scene(1068, DENSE_CHAIN_POINTS, 6, vis_mode=1, outliers=0.2)
+    sh = _schedule(sc)
+    assert (sh["flow"], sh["nt"], sh["nF"]) == (0, 101, 6406), sh
+    sh = _schedule(H.Scene(1067, DENSE_CHAIN_POINTS, 6, vis_mode=1, outliers=0.2))
+    assert (sh["flow"], sh["nt"]) == (1, 100), sh
+    return sc
+
+
 def _shape(sc):
     sh = api.ba_describe(sc.problem())
     return {k: getattr(sh, k) for k, _ in sh._fields_}
@@ -224,7 +300,7 @@ class Case:
         self.shape = _shape(sc)
         self.x0 = R.pack(sc.params())
         self.lay = R.layout(sc)
-        assert self.lay.n <= 2500
+        assert self.lay.n <= R.DENSE_MAX or name in LARGE    # (past the cap: the reference's matrix-free path)
         if check:
             check(self.shape)
 
@@ -299,6 +375,13 @@ def _build(name):
     if name == "rejecting":       # rejected steps (radius / 2, / 4), an accept after a reject
         sc = S(12, 150, 4, seed=REJECTING_SEED, outliers=0.2)
         return Case(name, sc, n_iter=4, radius=REJECTING_RADIUS, check=_expect(dense=0))
+    if name == "dense_flow_wrap":    # the dataflow dense solve, more tasks than workers
+        return Case(name, _dense_flow_wrap(), check=_expect(dense=1, n_general_pts=3000, n_chunk_pts=0))
+    if name == "percam_radial3_band":    # the banded-arrow tile order over two chains
+        return Case(name, _percam_radial3_band(), check=_expect(dense=1, n_intr_active=47))
+    if name == "dense_chain_101":    # past the dataflow limit: the launch chain, dense_back_all_kernel
+        return Case(name, _dense_chain_101(),
+                    check=_expect(dense=1, n_general_pts=DENSE_CHAIN_POINTS, n_chunk_pts=0, rcs_dim=6406))
     raise KeyError(name)
 
 
@@ -309,9 +392,13 @@ CLAMPED_RADIUS = 1e1       # the far point's columns are ~1e-7 of the others
 # accept) with both Huber branches populated at every point
 REJECTING_SEED, REJECTING_RADIUS = 11, 1e7
 
+DENSE_CHAIN_POINTS = 6000  # 6 views each: ~34 observations per camera
 NAMES = ("one_block", "band_c4", "band_c4_pt", "band_arrow4", "dense_random", "dense_random_pt", "mixed",
          "long_track", "repeats", "two_chains", "snavely", "snavely_intr", "radial3", "per_cam_pinhole", "plain",
          "no_gauge", "clamped", "rejecting")
+# The many-tile dense scenes: the oracle runs them with 8 threads only (the factor of 6406 rows takes seconds)
+LARGE = ("dense_flow_wrap", "percam_radial3_band", "dense_chain_101")
+ALL_NAMES = NAMES + LARGE
 # The column class (camera, intrinsics, point) that holds the largest |g| entry at x_0, x_1, ..: the part of
 # the gradient reduction that gradient_max_norm of that trace entry witnesses (the reference's g, checked at
 # every iteration, so the coverage is pinned).  The plain scenes are camera-dominated nearly everywhere; the
@@ -335,6 +422,9 @@ GRADIENT_CLASS = {
     "no_gauge": ("cam", "cam", "cam", "cam"),
     "clamped": ("cam", "cam", "cam", "cam"),
     "rejecting": ("cam", "cam", "cam", "cam", "cam"),
+    "dense_flow_wrap": ("cam", "cam", "cam", "cam"),
+    "percam_radial3_band": ("cam", "cam", "cam", "cam"),
+    "dense_chain_101": ("cam", "cam", "cam", "cam"),
 }
 CAP_EXEMPT = ("no_gauge",)
 _cases = {}
@@ -456,8 +546,11 @@ def oracle_run(cs, threads):
 
 
 # ---- tests -------------------------------------------------------------------------------
-@pytest.mark.parametrize("threads", THREADS)
-@pytest.mark.parametrize("name", NAMES)
+def threads_of(name):
+    return (8,) if name in LARGE else THREADS
+
+
+@pytest.mark.parametrize("name,threads", [(name, t) for name in ALL_NAMES for t in threads_of(name)])
 def test_oracle_lm_step(name, threads):
     cs = case(name)
     check_run(cs, oracle_run(cs, threads))
@@ -468,9 +561,9 @@ def test_c_step_is_eight_times_the_oracle_worst_ratio():
     and accepted iteration (the reference steps are the cached ones of test_oracle_lm_step); C_STEP is the
     smallest power of two >= 8 x the maximum.  Prints the docstring's table (pytest -s)."""
     rows = {}
-    for name in NAMES:
+    for name in ALL_NAMES:
         cs = case(name)
-        for threads in THREADS:
+        for threads in threads_of(name):
             rec = []
             check_run(cs, oracle_run(cs, threads), record=rec)
             assert rec
@@ -494,6 +587,27 @@ def test_reference_condition_number_is_cond2():
     ref = R.lm_step(cs.sc, cs.x0, cs.x0, radius, cs.opts)
     Hm = R.normal_equations(cs.sc, cs.x0, cs.x0, radius, cs.opts)[0]
     assert abs(np.linalg.cond(Hm.astype(np.float64)) / ref["cond"] - 1) < 1e-9
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_matrix_free_reference_agrees_with_the_dense_one(name):
+    """The reference's two ways to y at x_0, on every scene small enough for both: each one's y has a
+    backward error <= 2^-59 under the other's H (the dense longdouble H; the matrix-free operator), and the
+    two condition numbers (eigvalsh of the dense fp64 H; Lanczos on the sparse one) agree to 1e-3."""
+    cs = case(name)
+    sc, opts, radius = cs.sc, cs.opts, cs.opts.initial_trust_region_radius
+    Hm, g, Js, _, _, _ = R.normal_equations(sc, cs.x0, cs.x0, radius, opts)
+    y_dense, _, H64 = R._solve(Hm, g)
+    ev = np.linalg.eigvalsh(H64)
+    Js2, _, _, _, diag, g2 = R.scaled_rows(sc, cs.x0, cs.x0, radius, opts)
+    assert np.array_equal(g, g2) and np.array_equal(Js, Js2)
+    op = R.Operator(cs.lay, Js2, diag)
+    y_free, be, cond = R.solve_matrix_free(op, g2, 3 * sc.n_pt)
+    assert be <= R.BACKWARD_ERROR_MAX
+    assert op.backward_error(y_dense, g) <= 2.0 ** -59
+    hn, gn = np.abs(Hm).sum(axis=1).max(), np.abs(g).max()
+    assert float(np.abs(g - Hm @ y_free).max() / (hn * np.abs(y_free).max() + gn)) <= 2.0 ** -59
+    assert abs(cond / float(ev[-1] / ev[0]) - 1) <= 1e-3, (cond, ev[-1] / ev[0])
 
 
 def test_clamped_scene_clamps():

@@ -72,13 +72,18 @@ def _check(ctx, cs, solver=None, tile_rows=None):
         plan.close()
 
 
-@pytest.mark.parametrize("name", T.NAMES)
+@pytest.mark.parametrize("name", T.ALL_NAMES)
 def test_gpu_lm_step(ctx, name):
-    _check(ctx, T.case(name))
+    _check(ctx, T.case(name), DENSE if name in T.LARGE else None)
 
 
-@pytest.mark.parametrize("engine", list(ENGINES))
-@pytest.mark.parametrize("name", T.STARRED)
+# dense_flow_wrap (21 block columns) under the launch chain: several kDenseW groups with their trailing
+# updates and the dense_back_kernel loop; under the dense engines only, not under all thirteen
+DENSE_ENGINES = ("default", "dense_rcs", "dense_chain")
+
+
+@pytest.mark.parametrize("name,engine", [(name, e) for name in T.STARRED for e in ENGINES] +
+                         [("dense_flow_wrap", e) for e in DENSE_ENGINES])
 def test_gpu_lm_step_engine_shapes(name, engine):
     cs = T.case(name)
     flags, solver, tile_rows = ENGINES[engine]
