@@ -55,6 +55,8 @@ SFM_RCS_BCR, SFM_RCS_DENSE, SFM_RCS_SEQ_BAND = 0, 1, 2
 SFM_TRI_LINEAR, SFM_TRI_ROBUST = 0, 1
 SFM_TRI_OK, SFM_TRI_SHORT, SFM_TRI_ANGLE, SFM_TRI_INFINITE = 0, 1, 2, 3
 
+SFM_RESECT_OK, SFM_RESECT_FEW, SFM_RESECT_NO_MODEL = 0, 1, 2
+
 SFM_MATCH_RATIO = 0
 SFM_MATCH_MUTUAL = 1
 SFM_MATCH_CASCADE = 2
@@ -235,6 +237,16 @@ class FMatrixResult(C.Structure):
                 ("n_inliers", C.c_int32), ("iterations", C.c_int32)]
 
 
+class ResectOpts(C.Structure):
+    _fields_ = [("precision", C.c_double), ("max_iterations", C.c_int32), ("refine_iterations", C.c_int32)]
+
+
+class ResectResult(C.Structure):
+    _fields_ = [("pose", C.c_double * 6), ("pose_model", C.c_double * 6), ("error_max", C.c_double),
+                ("min_nfa", C.c_double), ("n_inliers", C.c_int32), ("iterations", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SparseFilterStats(C.Structure):
     _fields_ = [("n_pairs_in", C.c_int64), ("n_pairs_out", C.c_int64), ("n_matches_in", C.c_int64),
                 ("n_matches_out", C.c_int64)]
@@ -300,6 +312,13 @@ SIGNATURES = [
     ("sfm_tracks_destroy", C.c_int, [C.c_void_p]),
     ("sfm_sparse_tracks", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(TracksOpts),
                                     C.POINTER(C.c_void_p)]),
+    ("sfm_resect_default_options", None, [C.POINTER(ResectOpts)]),
+    ("sfm_resect", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i64p, f64p, f64p, i32p, f64p, C.c_int32, i32p,
+                             C.POINTER(ResectOpts), C.POINTER(ResectResult), i32p]),
+    ("sfm_resect_host", C.c_int, [C.c_int32, C.c_int64, i64p, f64p, f64p, i32p, f64p, C.c_int32, i32p,
+                                  C.POINTER(ResectOpts), C.POINTER(ResectResult), i32p]),
+    ("sfm_resect_p3p", C.c_int, [f64p, f64p, f64p, i32p]),
+    ("sfm_resect_gather", C.c_int, [C.POINTER(BAProblem), f64p, u8p, i32p, C.c_int32, i64p, f64p, f64p]),
     ("sfm_ba_intr_width", C.c_int, [C.c_int32]),
     ("sfm_ba_partition", C.c_int, [C.POINTER(BAProblem), C.c_int32, i64p, i64p]),
     ("sfm_ba_describe", C.c_int, [C.POINTER(BAProblem), C.c_int32, C.c_int32, C.POINTER(BAPlanShape)]),

@@ -441,6 +441,81 @@ def triangulate(ctx, problem, extr, intr, opts=None):
                 stats={f: getattr(stats, f) for f, _ in abi.TriStats._fields_})
 
 
+def resect_default_options():
+    o = abi.ResectOpts()
+    abi.load().sfm_resect_default_options(C.byref(o))
+    return o
+
+
+def resect(ctx, camera_model, X_list, uv_list, img_intr, intr, wh, opts=None):
+    """sfm_resect (ctx None: sfm_resect_host, on the CPU) over a list of images:
+    X_list[q] (n_q, 3) world points and uv_list[q] (n_q, 2) pixels, img_intr[q]
+    the image's block of intr, wh[q] = (w, h).  One dict per image: pose,
+    pose_model (angle-axis, t), error_max, min_nfa, n_inliers, iterations,
+    status (SFM_RESECT_*), inliers.  opts: ResectOpts (None: the defaults)."""
+    n_img = len(X_list)
+    off = np.zeros(n_img + 1, np.int64)
+    off[1:] = np.cumsum([len(x) for x in X_list])
+    n = int(off[-1])
+    X = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).reshape(-1, 3) for x in X_list])
+                             if n else np.zeros((1, 3)))
+    uv = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).reshape(-1, 2) for x in uv_list])
+                              if n else np.zeros((1, 2)))
+    img_intr = np.ascontiguousarray(np.asarray(img_intr, np.int32).reshape(-1))
+    intr = np.ascontiguousarray(np.asarray(intr, np.float64).reshape(-1))
+    iw = abi.load().sfm_ba_intr_width(camera_model)
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    assert len(img_intr) == n_img and len(wh) == 2 * n_img
+    res = (abi.ResectResult * max(n_img, 1))()
+    inl = np.full(max(n, 1), -1, np.int32)
+    args = (camera_model, n_img, abi.ptr(off, abi.i64p), abi.ptr(X, abi.f64p), abi.ptr(uv, abi.f64p),
+            abi.ptr(img_intr, abi.i32p), abi.ptr(intr, abi.f64p), len(intr) // iw if iw else 0,
+            abi.ptr(wh, abi.i32p), C.byref(opts) if opts is not None else None, res, abi.ptr(inl, abi.i32p))
+    if ctx is None:
+        _check(abi.load().sfm_resect_host(*args), "sfm_resect_host")
+    else:
+        _check(ctx.lib.sfm_resect(ctx.h, *args), "sfm_resect")
+    out = []
+    for q in range(n_img):
+        r = res[q]
+        out.append({"pose": np.array(r.pose[:]), "pose_model": np.array(r.pose_model[:]), "error_max": r.error_max,
+                    "min_nfa": r.min_nfa, "n_inliers": r.n_inliers, "iterations": r.iterations, "status": r.status,
+                    "inliers": inl[off[q]:off[q] + r.n_inliers].copy()})
+    return out
+
+
+def resect_p3p(b, X):
+    """sfm_resect_p3p: the models [(R (3, 3), t (3,)), ...] that map the world
+    points X (3, 3) onto the unit bearings b (3, 3)."""
+    b = np.ascontiguousarray(b, np.float64).reshape(9)
+    X = np.ascontiguousarray(X, np.float64).reshape(9)
+    Rt = np.zeros(48)
+    n = C.c_int32()
+    _check(abi.load().sfm_resect_p3p(abi.ptr(b, abi.f64p), abi.ptr(X, abi.f64p), abi.ptr(Rt, abi.f64p),
+                                     C.byref(n)), "sfm_resect_p3p")
+    return [(Rt[12 * m:12 * m + 9].reshape(3, 3).copy(), Rt[12 * m + 9:12 * m + 12].copy()) for m in range(n.value)]
+
+
+def resect_gather(problem, X, pt_ok, images, counts_only=False):
+    """sfm_resect_gather: for each image of `images`, its observations whose
+    point is flagged in pt_ok, in the problem's order: (off, X3 [n, 3],
+    uv [n, 2]), or off alone with counts_only."""
+    images = np.ascontiguousarray(np.asarray(images, np.int32).reshape(-1))
+    pt_ok = np.ascontiguousarray(np.asarray(pt_ok).astype(np.uint8).reshape(-1))
+    X = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+    off = np.zeros(len(images) + 1, np.int64)
+    lib = abi.load()
+    head = (C.byref(problem), abi.ptr(X, abi.f64p), abi.ptr(pt_ok, abi.u8p), abi.ptr(images, abi.i32p), len(images),
+            abi.ptr(off, abi.i64p))
+    _check(lib.sfm_resect_gather(*head, None, None), "sfm_resect_gather")
+    if counts_only:
+        return off
+    X3 = np.zeros((max(int(off[-1]), 1), 3))
+    uv = np.zeros((max(int(off[-1]), 1), 2))
+    _check(lib.sfm_resect_gather(*head, abi.ptr(X3, abi.f64p), abi.ptr(uv, abi.f64p)), "sfm_resect_gather")
+    return off, X3[:off[-1]], uv[:off[-1]]
+
+
 def tracks_default_options():
     o = abi.TracksOpts()
     abi.load().sfm_tracks_default_options(C.byref(o))

@@ -69,9 +69,12 @@ __host__ __device__ inline bool track_finite(double x) { return fabs(x) <= 1.797
 
 // 1 / depth: the one operation host and device do differently (the solver's
 // rcp_nr on the device, a division on the host), so the two agree to
-// rounding, not bit for bit
+// rounding, not bit for bit.  A file that defines SFM_DEPTH_RCP_DIVIDES before
+// including this one divides on the device too (resect.hip: the errors of a
+// minimal sample's own correspondences are rounding noise, and their order
+// feeds the next samples, so there the two paths must round alike).
 __host__ __device__ inline double depth_rcp(double z) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(SFM_DEPTH_RCP_DIVIDES)
     return rcp_nr(z);
 #else
     return 1.0 / z;
@@ -84,21 +87,13 @@ __host__ __device__ inline double depth_rcp(double z) {
 // linearize() is the one other copy in csrc/: its projection is fused with
 // the Jacobians it feeds, and that kernel code is measured and pinned bit for
 // bit, so it does not call this.
+// The part from P on: the model's pixel at the camera-frame point P, minus the
+// observation.  One definition for project_residual below and the camera
+// resection's error and refit (resect_pose.h), which has P from a rotation
+// matrix and no CamPre.
 template <int CM>
-__host__ __device__ inline void project_residual(const CamPre& cp, const double* in, const double* X, double u0,
-                                                 double u1, double (&P)[3], double& r0, double& r1) {
-    const double* u = cp.u;
-    const double cr0 = u[1] * X[2] - u[2] * X[1], cr1 = u[2] * X[0] - u[0] * X[2],
-                 cr2 = u[0] * X[1] - u[1] * X[0];
-    if (cp.small != 0.0) {
-        P[0] = X[0] + cr0; P[1] = X[1] + cr1; P[2] = X[2] + cr2;
-    } else {
-        const double tmp = (u[0] * X[0] + u[1] * X[1] + u[2] * X[2]) * cp.omc;
-        P[0] = X[0] * cp.c + cr0 * cp.s + u[0] * tmp;
-        P[1] = X[1] * cp.c + cr1 * cp.s + u[1] * tmp;
-        P[2] = X[2] * cp.c + cr2 * cp.s + u[2] * tmp;
-    }
-    P[0] += cp.t[0]; P[1] += cp.t[1]; P[2] += cp.t[2];
+__host__ __device__ inline void pixel_residual(const double* in, const double (&P)[3], double u0, double u1,
+                                               double& r0, double& r1) {
     const double iz = depth_rcp(P[2]);
     if constexpr (CM == SFM_CAM_RADIAL3) {
         const double xu = P[0] * iz, yu = P[1] * iz;
@@ -117,6 +112,24 @@ __host__ __device__ inline void project_residual(const CamPre& cp, const double*
         r0 = in[0] * x + in[2] - u0;
         r1 = in[1] * y + in[3] - u1;
     }
+}
+
+template <int CM>
+__host__ __device__ inline void project_residual(const CamPre& cp, const double* in, const double* X, double u0,
+                                                 double u1, double (&P)[3], double& r0, double& r1) {
+    const double* u = cp.u;
+    const double cr0 = u[1] * X[2] - u[2] * X[1], cr1 = u[2] * X[0] - u[0] * X[2],
+                 cr2 = u[0] * X[1] - u[1] * X[0];
+    if (cp.small != 0.0) {
+        P[0] = X[0] + cr0; P[1] = X[1] + cr1; P[2] = X[2] + cr2;
+    } else {
+        const double tmp = (u[0] * X[0] + u[1] * X[1] + u[2] * X[2]) * cp.omc;
+        P[0] = X[0] * cp.c + cr0 * cp.s + u[0] * tmp;
+        P[1] = X[1] * cp.c + cr1 * cp.s + u[1] * tmp;
+        P[2] = X[2] * cp.c + cr2 * cp.s + u[2] * tmp;
+    }
+    P[0] += cp.t[0]; P[1] += cp.t[1]; P[2] += cp.t[2];
+    pixel_residual<CM>(in, P, u0, u1, r0, r1);
 }
 
 // The reject code of an observation from what project_residual gave: depth

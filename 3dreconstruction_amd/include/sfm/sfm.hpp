@@ -6,6 +6,8 @@
 //   LocalFrame/GlobalFrame src/frame/LocalFrame.h:19-83, GlobalFrame.h:15-160
 //   Triangulator          every world point from its track and the current
 //                         poses (triangulator.hpp; sfm_triangulate)
+//   Localizer             the pose of an image from the world points it observes
+//                         (localizer.hpp; sfm_resect)
 //   TracksBuilder         OpenMVG's tracks::TracksBuilder, the first step of the
 //                         engine reconstruction() runs (sparseBuilder.cpp:1474-1508):
 //                         pairwise matches into tracks (tracks.hpp; sfm_tracks_build)
@@ -33,6 +35,7 @@
 #include "actuator.hpp"
 #include "adjuster.hpp"
 #include "frames.hpp"
+#include "localizer.hpp"
 #include "tracks.hpp"
 #include "triangulator.hpp"
 #include "world.hpp"
@@ -141,6 +144,25 @@ class Triangulator : public BasicTriangulator<GpuTriBackend> {
    public:
     explicit Triangulator(Context& ctx = Context::thread_default())
         : BasicTriangulator<GpuTriBackend>(GpuTriBackend{&ctx}) {}
+};
+
+// ---------------------------------------------------------------------------
+// Localizer (localizer.hpp) on the GPU: sfm_resect
+// ---------------------------------------------------------------------------
+struct GpuResectBackend {
+    Context* ctx;
+    int resect(int32_t cm, int64_t n_img, const int64_t* off, const double* X, const double* uv,
+               const int32_t* img_intr, const double* intr, int32_t n_intr, const int32_t* wh,
+               const sfm_resect_opts& o, sfm_resect_result* results, int32_t* inliers) const {
+        return sfm_resect(ctx->get(), cm, n_img, off, X, uv, img_intr, intr, n_intr, wh, &o, results, inliers);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+class Localizer : public BasicLocalizer<GpuResectBackend> {
+   public:
+    explicit Localizer(Context& ctx = Context::thread_default())
+        : BasicLocalizer<GpuResectBackend>(GpuResectBackend{&ctx}) {}
 };
 
 // ---------------------------------------------------------------------------

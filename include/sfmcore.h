@@ -95,7 +95,7 @@ typedef struct sfm_ctx_opts {
  * every rank of a sharded solve then returns SFM_ERR_DEVICE together instead
  * of the others waiting in the next collective. */
 #define SFM_CTX_DIAG_FAIL_SOLVE_WAIT 4
-/* Measurement: sfm_fmatrix_ac, sfm_triangulate and sfm_tracks_build bracket their kernels with
+/* Measurement: sfm_fmatrix_ac, sfm_triangulate, sfm_tracks_build and sfm_resect bracket their kernels with
  * HIP events (after draining the uploads) so that sfm_ctx_last_kernel_ms can
  * report the kernels alone.  Off by default: the extra stream synchronisation and event pair are
  * not part of the filter's production path. */
@@ -683,8 +683,8 @@ int sfm_fmatrix_ac(sfm_ctx* ctx, int64_t n_pairs, const int64_t* off, const doub
                    sfm_fmatrix_result* results, int32_t* inliers);
 
 /* Device time (HIP events on the context's stream) of the kernel(s) of the
- * context's last sfm_fmatrix_ac, sfm_triangulate or sfm_tracks_build (also
- * through sfm_sparse_tracks) call, without its host
+ * context's last sfm_fmatrix_ac, sfm_triangulate, sfm_tracks_build (also
+ * through sfm_sparse_tracks) or sfm_resect call, without its host
  * normalisation, uploads and downloads (measurement; no reference counterpart).  Only a
  * context created with SFM_CTX_TIME_KERNELS times it; -1 otherwise. */
 int sfm_ctx_last_kernel_ms(sfm_ctx* ctx, double* ms);
@@ -935,6 +935,110 @@ int sfm_tracks_destroy(sfm_tracks* t);
  * A match naming a view that sfm_data.json lacks is SFM_ERR_INVALID_ARG. */
 int sfm_sparse_tracks(sfm_ctx* ctx, const char* matches_dir, const char* matches_file,
                       const sfm_tracks_opts* opts, sfm_tracks** out);
+
+/* ------------------------------------------------------------------------ */
+/* Camera resection                                                          */
+/* The pose of an image from 2D-3D correspondences: what OpenMVG's           */
+/* incremental engine (reconstruction() with engine_name "INCREMENTAL",      */
+/* sparseBuilder.cpp:1289,1477) does for every image it adds:                */
+/* SfM_Localizer::Localize (AC-RANSAC over a P3P solver, 4096 iterations, no */
+/* upper threshold) and RefinePose on the inliers.  Restated from its        */
+/* published code, parity unpinned.  n_img independent        */
+/* problems; the GPU runs one workgroup per image.                           */
+/*                                                                          */
+/* Problem q: correspondences k = off[q] .. off[q+1]-1 (n of them), world    */
+/* point X[3k..], pixel uv[2k..], intrinsics block intr + iw * img_intr[q]   */
+/* (iw = sfm_ba_intr_width(camera_model)), image size wh[2q..] = (w, h).     */
+/*   bearing   of a pixel: sfm_triangulate's.  A correspondence whose        */
+/*             bearing is not finite never enters a sample and has error     */
+/*             +inf.  The others, in order, are the list samples draw from.  */
+/*   P3P       3 correspondences -> at most 4 models (R, t), P = R X + t:    */
+/*             Grunert's quartic in the ratio of two distances, its real     */
+/*             roots by Ferrari's resolvent and 2 Newton steps, the three    */
+/*             distances polished by 2 Newton steps on the cosine laws and   */
+/*             kept when all are positive, R and t by aligning the two       */
+/*             triangles' frames.  Only + - * / and sqrt.  0 models for a    */
+/*             collinear or repeated sample.                                 */
+/*   error     of a correspondence under a model: |r|^2 in px^2, r the       */
+/*             camera model's residual at P; +inf when r is not finite or P  */
+/*             is not in front (P2 > 0; P2 < 0 for SNAVELY).                 */
+/*   AC-RANSAC OpenMVG's ACRANSAC as sfm_fmatrix_ac restates it: the         */
+/*             mt19937(default_seed) stream from position 0 per problem, the */
+/*             same uniform_int restatement, two sampling modes, 10 %        */
+/*             iteration reserve, focused resampling and tie rules.  A model */
+/*             counts as found with more than 2.5 * 3 errors under the       */
+/*             bound.  NFA(k) = loge0 + logalpha (k-3) + logcombi(k, n) +    */
+/*             logcombi(3, k), k = 4 .. m, over the m errors under the bound */
+/*             in ascending (error, index) order, logalpha = logalpha0 +     */
+/*             log10(e_k + FLT_EPSILON), logalpha0 = log10(pi / (w h)),      */
+/*             loge0 = log10(4 (n - 3)); the two logcombi tables are rounded */
+/*             to float, as OpenMVG's.  The bound is precision^2;            */
+/*             precision <= 0 or +inf: none (every finite error).            */
+/*             Kept iff min_nfa < 0 and n_inliers > 7.                       */
+/*   refit     on a kept problem's inliers, from the RANSAC model: up to     */
+/*             refine_iterations Gauss-Newton steps on (R <- exp[d]x R,      */
+/*             t += d_t) with the camera model's residual and its analytic   */
+/*             Jacobian, no loss; an inlier behind the camera (or with a     */
+/*             residual that is not finite) at an iterate is skipped; stops  */
+/*             once |d|^2 < 1e-24.  A singular 6x6 system (or a rotation     */
+/*             step above 1 rad) leaves the RANSAC model in place.  The      */
+/*             inlier set is not re-evaluated after the refit.               */
+/* status: SFM_RESECT_FEW (n <= 3, or fewer than 4 finite bearings:          */
+/* everything 0), SFM_RESECT_NO_MODEL (not kept: n_inliers 0, both poses and */
+/* error_max 0, min_nfa the best seen, +inf when none), SFM_RESECT_OK.       */
+/* Two device runs give the same bits.  Host and device run the same         */
+/* statements and differ by rounding only.                                   */
+/* ------------------------------------------------------------------------ */
+#define SFM_RESECT_OK       0
+#define SFM_RESECT_FEW      1
+#define SFM_RESECT_NO_MODEL 2
+typedef struct sfm_resect_opts {
+    double  precision;          /* px; <= 0 or +inf: no upper bound (the engine) */
+    int32_t max_iterations;     /* 4096 (>= 1)                                    */
+    int32_t refine_iterations;  /* 10 (>= 0)                                      */
+} sfm_resect_opts;
+typedef struct sfm_resect_result {
+    double  pose[6];        /* refined: angle-axis, then t (the extrinsics layout) */
+    double  pose_model[6];  /* the RANSAC model before the refit                   */
+    double  error_max;      /* px: square root of the a-contrario threshold        */
+    double  min_nfa;        /* log10 NFA of the best model                         */
+    int32_t n_inliers;
+    int32_t iterations;     /* RANSAC iterations run                               */
+    int32_t status;         /* SFM_RESECT_*                                        */
+    int32_t reserved;
+} sfm_resect_result;
+/* [cpu] {0 (no bound), 4096, 10}; NULL opts below select them. */
+void sfm_resect_default_options(sfm_resect_opts* opts);
+/* inliers[off[q] + t], t < results[q].n_inliers: the inliers (indices into
+ * the problem's list) in ascending (error, index) order at the RANSAC model;
+ * the rest of inliers[] is left alone.  Every argument check runs on the host
+ * before any device call: a null pointer, negative counts, off[0] != 0 or off
+ * not monotone, an unknown camera_model, img_intr outside [0, n_intr), a
+ * non-positive image size, max_iterations < 1, refine_iterations < 0 or a NaN
+ * precision: SFM_ERR_INVALID_ARG; n_img or off[n_img] >= 2^31, or a problem
+ * drawing more than 2^18 random numbers: SFM_ERR_UNSUPPORTED.  Problems of
+ * any size (the sort moves from LDS to global memory above 8192
+ * correspondences).  It does not shard.  A context created with
+ * SFM_CTX_TIME_KERNELS reports the kernel's device time through
+ * sfm_ctx_last_kernel_ms. */
+int sfm_resect(sfm_ctx* ctx, int32_t camera_model, int64_t n_img, const int64_t* off /* [n_img+1] */,
+               const double* X /* [3*n] */, const double* uv /* [2*n] */, const int32_t* img_intr /* [n_img] */,
+               const double* intr /* [iw*n_intr] */, int32_t n_intr, const int32_t* wh /* [2*n_img] */,
+               const sfm_resect_opts* opts, sfm_resect_result* results /* [n_img] */, int32_t* inliers /* [n] */);
+/* [cpu] The same on the host, a serial loop over the same statements. */
+int sfm_resect_host(int32_t camera_model, int64_t n_img, const int64_t* off, const double* X, const double* uv,
+                    const int32_t* img_intr, const double* intr, int32_t n_intr, const int32_t* wh,
+                    const sfm_resect_opts* opts, sfm_resect_result* results, int32_t* inliers);
+/* [cpu] The minimal solver alone: unit bearings b[3i..] and world points
+ * X[3i..], i < 3; *n models, model m = Rt[m][0..8] (R row-major), Rt[m][9..11] (t). */
+int sfm_resect_p3p(const double b[9], const double X[9], double Rt[4][12], int32_t* n);
+/* [cpu] The 2D-3D correspondences of the n_images images listed in images[]
+ * (each in [0, prob->n_img)): the observations of image images[q] whose point
+ * p has pt_ok[p] != 0, in the problem's order, as off[n_images+1] and, unless
+ * NULL, X3[3k..] = X[3p..] and uv[2k..].  With X3 and uv NULL it returns the
+ * counts only (over every image: which images can be resected next). */
+int sfm_resect_gather(const sfm_ba_problem* prob, const double* X, const uint8_t* pt_ok, const int32_t* images,
+                      int32_t n_images, int64_t* off, double* X3, double* uv);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
