@@ -247,6 +247,17 @@ class ResectResult(C.Structure):
                 ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RelposeOpts(C.Structure):
+    _fields_ = [("precision", C.c_double), ("max_iterations", C.c_int32), ("reserved", C.c_int32),
+                ("front_ratio", C.c_double)]
+
+
+class RelposeResult(C.Structure):
+    _fields_ = [("E", C.c_double * 9), ("pose", C.c_double * 6), ("error_max", C.c_double),
+                ("min_nfa", C.c_double), ("angle_median", C.c_double), ("n_inliers", C.c_int32),
+                ("n_front", C.c_int32), ("iterations", C.c_int32), ("status", C.c_int32)]
+
+
 class SparseFilterStats(C.Structure):
     _fields_ = [("n_pairs_in", C.c_int64), ("n_pairs_out", C.c_int64), ("n_matches_in", C.c_int64),
                 ("n_matches_out", C.c_int64)]
@@ -319,6 +330,12 @@ SIGNATURES = [
                                   C.POINTER(ResectOpts), C.POINTER(ResectResult), i32p]),
     ("sfm_resect_p3p", C.c_int, [f64p, f64p, f64p, i32p]),
     ("sfm_resect_gather", C.c_int, [C.POINTER(BAProblem), f64p, u8p, i32p, C.c_int32, i64p, f64p, f64p]),
+    ("sfm_relpose_default_options", None, [C.POINTER(RelposeOpts)]),
+    ("sfm_relpose", C.c_int, [C.c_void_p, C.c_int32, C.c_int64, i64p, f64p, i32p, f64p, C.c_int32, i32p,
+                              C.POINTER(RelposeOpts), C.POINTER(RelposeResult), i32p]),
+    ("sfm_relpose_host", C.c_int, [C.c_int32, C.c_int64, i64p, f64p, i32p, f64p, C.c_int32, i32p,
+                                   C.POINTER(RelposeOpts), C.POINTER(RelposeResult), i32p]),
+    ("sfm_relpose_5pt", C.c_int, [f64p, f64p, f64p, i32p]),
     ("sfm_ba_intr_width", C.c_int, [C.c_int32]),
     ("sfm_ba_partition", C.c_int, [C.POINTER(BAProblem), C.c_int32, i64p, i64p]),
     ("sfm_ba_describe", C.c_int, [C.POINTER(BAProblem), C.c_int32, C.c_int32, C.POINTER(BAPlanShape)]),

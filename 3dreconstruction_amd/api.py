@@ -516,6 +516,61 @@ def resect_gather(problem, X, pt_ok, images, counts_only=False):
     return off, X3[:off[-1]], uv[:off[-1]]
 
 
+def relpose_default_options():
+    o = abi.RelposeOpts()
+    abi.load().sfm_relpose_default_options(C.byref(o))
+    return o
+
+
+def relpose(ctx, camera_model, xy_list, pair_intr, intr, wh, opts=None):
+    """sfm_relpose (ctx None: sfm_relpose_host, on the CPU) over a list of image
+    pairs: xy_list[q] (n_q, 4) matched pixels (x_I, y_I, x_J, y_J), pair_intr[q]
+    = (block of image I, block of image J) in intr, wh[q] = (w_I, h_I, w_J, h_J).
+    One dict per pair: E (3, 3), pose (angle-axis, t), error_max, min_nfa,
+    angle_median, n_inliers, n_front, iterations, status (SFM_RELPOSE_*),
+    inliers.  opts: RelposeOpts (None: the defaults)."""
+    n_pairs = len(xy_list)
+    off = np.zeros(n_pairs + 1, np.int64)
+    off[1:] = np.cumsum([len(x) for x in xy_list])
+    n = int(off[-1])
+    xy = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).reshape(-1, 4) for x in xy_list])
+                              if n else np.zeros((1, 4)))
+    pair_intr = np.ascontiguousarray(np.asarray(pair_intr, np.int32).reshape(-1))
+    intr = np.ascontiguousarray(np.asarray(intr, np.float64).reshape(-1))
+    iw = abi.load().sfm_ba_intr_width(camera_model)
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    assert len(pair_intr) == 2 * n_pairs and len(wh) == 4 * n_pairs
+    res = (abi.RelposeResult * max(n_pairs, 1))()
+    inl = np.full(max(n, 1), -1, np.int32)
+    args = (camera_model, n_pairs, abi.ptr(off, abi.i64p), abi.ptr(xy, abi.f64p), abi.ptr(pair_intr, abi.i32p),
+            abi.ptr(intr, abi.f64p), len(intr) // iw if iw else 0, abi.ptr(wh, abi.i32p),
+            C.byref(opts) if opts is not None else None, res, abi.ptr(inl, abi.i32p))
+    if ctx is None:
+        _check(abi.load().sfm_relpose_host(*args), "sfm_relpose_host")
+    else:
+        _check(ctx.lib.sfm_relpose(ctx.h, *args), "sfm_relpose")
+    out = []
+    for q in range(n_pairs):
+        r = res[q]
+        out.append({"E": np.array(r.E[:]).reshape(3, 3), "pose": np.array(r.pose[:]), "error_max": r.error_max,
+                    "min_nfa": r.min_nfa, "angle_median": r.angle_median, "n_inliers": r.n_inliers,
+                    "n_front": r.n_front, "iterations": r.iterations, "status": r.status,
+                    "inliers": inl[off[q]:off[q] + r.n_inliers].copy()})
+    return out
+
+
+def relpose_5pt(bI, bJ):
+    """sfm_relpose_5pt: the essential matrices [(3, 3), ...] with bJ[i]' E bI[i] = 0
+    for the five unit bearing pairs bI, bJ (5, 3)."""
+    bI = np.ascontiguousarray(bI, np.float64).reshape(15)
+    bJ = np.ascontiguousarray(bJ, np.float64).reshape(15)
+    E = np.zeros(90)
+    n = C.c_int32()
+    _check(abi.load().sfm_relpose_5pt(abi.ptr(bI, abi.f64p), abi.ptr(bJ, abi.f64p), abi.ptr(E, abi.f64p),
+                                      C.byref(n)), "sfm_relpose_5pt")
+    return [E[9 * m:9 * m + 9].reshape(3, 3).copy() for m in range(n.value)]
+
+
 def tracks_default_options():
     o = abi.TracksOpts()
     abi.load().sfm_tracks_default_options(C.byref(o))

@@ -81,7 +81,7 @@ __host__ __device__ double bisect(double lo, double hi, double q3, double r2, bo
 
 // real roots of P[0] + P[1] x + P[2] x^2 + P[3] x^3 (1 or 3, ascending when 3);
 // 0 when P[0] == 0 (the 7-point caller's rule)
-__host__ __device__ int solve_cubic(const double P[4], double roots[3]) {
+[[maybe_unused]] __host__ __device__ int solve_cubic(const double P[4], double roots[3]) {
     if (P[0] == 0.0) return 0;
     const double a = P[2] / P[3], b = P[1] / P[3], c = P[0] / P[3];
     const double q = a * a - 3.0 * b;

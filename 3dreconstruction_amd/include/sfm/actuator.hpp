@@ -19,6 +19,9 @@
 //     RANSAC error measure and pixel threshold convention), plus recoverPose's
 //     cheirality / distance test in init, and the PnP inlier count = global
 //     matches reprojecting within pnp_reproj_px (solvePnPRansac's 8.0).
+//     The estimators themselves exist as batch stages outside this loop:
+//     RelativePoser (relative_pose.hpp, sfm_relpose) for the first two images
+//     and Localizer (localizer.hpp, sfm_resect) for every later one.
 //   * triangulatePoints (:217-219) is linear DLT (smallest eigenvector of
 //     AᵀA) on normalised coordinates, as OpenCV's, in double.
 // Keypoint -> world point bookkeeping and the image / world-point order are

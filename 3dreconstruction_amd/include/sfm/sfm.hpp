@@ -8,6 +8,9 @@
 //                         poses (triangulator.hpp; sfm_triangulate)
 //   Localizer             the pose of an image from the world points it observes
 //                         (localizer.hpp; sfm_resect)
+//   RelativePoser         the relative pose of image pairs from their matches and
+//                         the engine's choice of the initial pair
+//                         (relative_pose.hpp; sfm_relpose)
 //   TracksBuilder         OpenMVG's tracks::TracksBuilder, the first step of the
 //                         engine reconstruction() runs (sparseBuilder.cpp:1474-1508):
 //                         pairwise matches into tracks (tracks.hpp; sfm_tracks_build)
@@ -36,6 +39,7 @@
 #include "adjuster.hpp"
 #include "frames.hpp"
 #include "localizer.hpp"
+#include "relative_pose.hpp"
 #include "tracks.hpp"
 #include "triangulator.hpp"
 #include "world.hpp"
@@ -163,6 +167,25 @@ class Localizer : public BasicLocalizer<GpuResectBackend> {
    public:
     explicit Localizer(Context& ctx = Context::thread_default())
         : BasicLocalizer<GpuResectBackend>(GpuResectBackend{&ctx}) {}
+};
+
+// ---------------------------------------------------------------------------
+// RelativePoser (relative_pose.hpp) on the GPU: sfm_relpose
+// ---------------------------------------------------------------------------
+struct GpuRelposeBackend {
+    Context* ctx;
+    int relpose(int32_t cm, int64_t n_pairs, const int64_t* off, const double* xy, const int32_t* pair_intr,
+                const double* intr, int32_t n_intr, const int32_t* wh, const sfm_relpose_opts& o,
+                sfm_relpose_result* results, int32_t* inliers) const {
+        return sfm_relpose(ctx->get(), cm, n_pairs, off, xy, pair_intr, intr, n_intr, wh, &o, results, inliers);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+class RelativePoser : public BasicRelativePoser<GpuRelposeBackend> {
+   public:
+    explicit RelativePoser(Context& ctx = Context::thread_default())
+        : BasicRelativePoser<GpuRelposeBackend>(GpuRelposeBackend{&ctx}) {}
 };
 
 // ---------------------------------------------------------------------------

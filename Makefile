@@ -11,7 +11,8 @@ OBJS := $(patsubst $(CSRC)/%,build/%.o,$(SRCS))
 HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/*.hpp)
 
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
-     tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test
+     tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
+     tests/cpp/relpose_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -67,4 +68,9 @@ tests/cpp/tracks_facade_test: tests/cpp/tracks_test.cpp $(wildcard $(PKG)/includ
 # sfm::Localizer on the host backend: csrc/resect.cpp's host path compiled in
 # (no library, no HIP runtime: host only)
 tests/cpp/resect_test: tests/cpp/resect_test.cpp $(CSRC)/resect.cpp $(HDRS)
+	g++ -O2 -std=c++17 -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $<
+
+# sfm::RelativePoser on the host backend: csrc/relpose.cpp's host path compiled
+# in (no library, no HIP runtime: host only)
+tests/cpp/relpose_test: tests/cpp/relpose_test.cpp $(CSRC)/relpose.cpp $(HDRS)
 	g++ -O2 -std=c++17 -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $<

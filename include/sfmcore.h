@@ -95,7 +95,7 @@ typedef struct sfm_ctx_opts {
  * every rank of a sharded solve then returns SFM_ERR_DEVICE together instead
  * of the others waiting in the next collective. */
 #define SFM_CTX_DIAG_FAIL_SOLVE_WAIT 4
-/* Measurement: sfm_fmatrix_ac, sfm_triangulate, sfm_tracks_build and sfm_resect bracket their kernels with
+/* Measurement: sfm_fmatrix_ac, sfm_triangulate, sfm_tracks_build, sfm_resect and sfm_relpose bracket their kernels with
  * HIP events (after draining the uploads) so that sfm_ctx_last_kernel_ms can
  * report the kernels alone.  Off by default: the extra stream synchronisation and event pair are
  * not part of the filter's production path. */
@@ -486,10 +486,12 @@ int sfm_synth_descriptors(int32_t n_img, int32_t n_kp, uint64_t seed,
 /* matching + 3*min filter run on the GPU matcher (sfm_match_dense MUTUAL);  */
 /* bundleAdjustment is a fresh BundleAdjuster over the whole world per call  */
 /* (:226-229) on the GPU solver (sfm_ba_solve).  The OpenCV geometry          */
-/* (findEssentialMat / recoverPose / solvePnPRansac) is out of scope: each   */
-/* image carries the pose that solver would return (pose_prior) and the      */
-/* inlier masks are geometric checks against the current poses (the C++      */
-/* header include/sfm/actuator.hpp documents each stand-in).                 */
+/* (findEssentialMat / recoverPose / solvePnPRansac) is not part of this     */
+/* loop: each image carries the pose that solver would return (pose_prior)   */
+/* and the inlier masks are geometric checks against the current poses (the  */
+/* C++ header include/sfm/actuator.hpp documents each stand-in).  The batch  */
+/* stages that estimate such poses are sfm_relpose ("Relative pose": the     */
+/* first two images) and sfm_resect ("Camera resection": every later one).   */
 /* ------------------------------------------------------------------------ */
 typedef struct sfm_seq_image {
     int32_t n_kp;
@@ -684,7 +686,7 @@ int sfm_fmatrix_ac(sfm_ctx* ctx, int64_t n_pairs, const int64_t* off, const doub
 
 /* Device time (HIP events on the context's stream) of the kernel(s) of the
  * context's last sfm_fmatrix_ac, sfm_triangulate, sfm_tracks_build (also
- * through sfm_sparse_tracks) or sfm_resect call, without its host
+ * through sfm_sparse_tracks), sfm_resect or sfm_relpose call, without its host
  * normalisation, uploads and downloads (measurement; no reference counterpart).  Only a
  * context created with SFM_CTX_TIME_KERNELS times it; -1 otherwise. */
 int sfm_ctx_last_kernel_ms(sfm_ctx* ctx, double* ms);
@@ -1039,6 +1041,150 @@ int sfm_resect_p3p(const double b[9], const double X[9], double Rt[4][12], int32
  * counts only (over every image: which images can be resected next). */
 int sfm_resect_gather(const sfm_ba_problem* prob, const double* X, const uint8_t* pt_ok, const int32_t* images,
                       int32_t n_images, int64_t* off, double* X3, double* uv);
+
+/* ------------------------------------------------------------------------ */
+/* Relative pose                                                             */
+/* The relative pose of an image pair from its 2D-2D matches: what OpenMVG's */
+/* incremental engine (reconstruction() with no initial pair given,          */
+/* sparseBuilder.cpp:1289,1302,1493) runs on every matched pair to choose    */
+/* the pair it starts from, and again on the winner: robustRelativePose      */
+/* (AC-RANSAC over the five-point essential-matrix solver, 4096 iterations)  */
+/* and the cheirality selection among the four motions.  Restated from its   */
+/* published code, parity unpinned.  n_pairs independent      */
+/* problems; the GPU runs one workgroup per pair.                            */
+/*                                                                          */
+/* Problem q: correspondences k = off[q] .. off[q+1]-1 (n of them), pixel    */
+/* xy[4k..] = (x_I, y_I, x_J, y_J), intrinsics blocks intr + iw *            */
+/* pair_intr[2q] (image I) and intr + iw * pair_intr[2q+1] (image J), iw =   */
+/* sfm_ba_intr_width(camera_model), image sizes wh[4q..] = (w_I, h_I, w_J,   */
+/* h_J): the layouts of sfm_fmatrix_ac.                                      */
+/*   bearing   of a pixel: sfm_triangulate's.  A correspondence with a       */
+/*             bearing that is not finite on either side never enters a      */
+/*             sample and has error +inf.  The others, in order, are the     */
+/*             list samples draw from.                                       */
+/*   5-point   5 bearing pairs -> at most 10 matrices E with b_J' E b_I = 0, */
+/*             Nister's formulation with these choices.  The 5x9 epipolar    */
+/*             system in E's row-major entries is brought to reduced row     */
+/*             echelon form by Gauss-Jordan elimination with complete        */
+/*             pivoting: each step takes the largest |entry| over the rows   */
+/*             not yet used and the columns not yet used, the lowest (row,   */
+/*             column) on a tie (pivoting on fixed columns would fail on a   */
+/*             forward motion).  Null vector u, u < 4, is 1 at the u-th free */
+/*             column, minus the reduced system's entries of that column at  */
+/*             the pivot columns, 0 elsewhere; X, Y, Z, W are the rows of    */
+/*             [1 -2 -3 -4; 2 1 -4 3; 3 4 1 -2; 4 -3 2 1] times the four,    */
+/*             each scaled to unit length, and E = x X + y Y + z Z + W.      */
+/*             det E = 0 and the nine entries of 2 E E' E - tr(E E') E = 0   */
+/*             are the rows of a 10x20 matrix over the monomials x3 y3 x2y   */
+/*             xy2 x2z x2 y2z y2 xyz xy xz2 xz x yz2 yz y z3 z2 z 1,         */
+/*             eliminated on its first 10 columns with partial pivoting (the */
+/*             largest |entry| of the column at or below the diagonal, the   */
+/*             lowest row on a tie).  Rows 4..9 give three equations [3] x + */
+/*             [3] y + [4] = 0 in polynomials of z; their determinant is the */
+/*             degree-10 polynomial.  Its real roots: the Sturm sequence,    */
+/*             counted at 256 equidistant points of [-B, B], B = min(1 + max */
+/*             |a_i / a_n|, 1e12) (Cauchy); a cell with several roots is     */
+/*             halved by Sturm counts (at most 64 times) until each root has */
+/*             a cell with a change of sign, then bisection on the sign,     */
+/*             ended when the midpoint is no longer inside or after 200      */
+/*             steps.  (x, y, 1) is the cross product of the two equations   */
+/*             with the largest third component; E is scaled to Frobenius    */
+/*             norm sqrt(2).  Only + - * / and sqrt; every loop is bounded.  */
+/*             0 models for a degenerate sample: a pivot not above 1e-12     */
+/*             (5x9; a repeated correspondence) or 1e-13 (10x20), or a       */
+/*             polynomial without a degree.  Models in ascending order of z. */
+/*   error     of a correspondence under E: with u^ the camera model's       */
+/*             pixel of a bearing with the distortion coefficients taken as  */
+/*             zero, and F the matrix with u^_J' F u^_I proportional to      */
+/*             b_J' E b_I: the squared distance in px of u^_J from the line  */
+/*             F u^_I; +inf when it is not finite.                           */
+/*   AC-RANSAC OpenMVG's ACRANSAC as sfm_fmatrix_ac restates it: the         */
+/*             mt19937(default_seed) stream from position 0 per problem, the */
+/*             same uniform_int restatement, two sampling modes, 10 %        */
+/*             iteration reserve, focused resampling and tie rules.  A model */
+/*             counts as found with more than 2.5 * 5 errors under the       */
+/*             bound.  NFA(k) = loge0 + logalpha (k-5) + logcombi(k, n) +    */
+/*             logcombi(5, k), k = 6 .. m, over the m errors under the bound */
+/*             in ascending (error, index) order, logalpha = logalpha0 +     */
+/*             0.5 log10(e_k + FLT_EPSILON), logalpha0 = log10(2 diag_J /    */
+/*             area_J) of image J's size, loge0 = log10(10 (n - 5)); the two */
+/*             logcombi tables are rounded to float, as OpenMVG's.  The      */
+/*             bound is precision^2; precision <= 0 or +inf: none (every     */
+/*             finite error).  Kept iff min_nfa < 0 and n_inliers > 12.      */
+/*   motion    of a kept E, in closed form without an SVD (Horn 1990):       */
+/*             t t' = tr(E E')/2 I - E E', t the row of its largest diagonal */
+/*             entry (the first on a tie) over the root of that entry; with  */
+/*             C the matrix of cofactors of E (rows e1 x e2, e2 x e0, e0 x   */
+/*             e1 of E's rows), Ra = (C - [t]x E) / (t.t) and its twisted    */
+/*             partner Rb = (C + [t]x E) / (t.t).  The four motions, in      */
+/*             order: (Ra, t), (Ra, -t), (Rb, t), (Rb, -t).  For each, the   */
+/*             inliers whose two-view triangulation (sfm_triangulate's       */
+/*             linear solve of the two bearings under [I | 0] and [R | t])   */
+/*             lies in front of both cameras are counted; in front is        */
+/*             sfm_resect's: P2 > 0 (P2 < 0 for SNAVELY).  The motion with   */
+/*             the largest count (the lowest index on a tie) wins iff the    */
+/*             largest of the other three counts over it is below            */
+/*             front_ratio; n_front is its count.  angle_median: the front   */
+/*             inliers of the winner in ascending (|b_I - R' b_J|^2, index)  */
+/*             order, the angle between b_I and R' b_J of the one at index   */
+/*             n_front / 2, in degrees.  There is no refit: the two-view     */
+/*             bundle adjustment is sfm_ba_solve's.                          */
+/* status: SFM_RELPOSE_FEW (n <= 5, or fewer than 6 pairs of finite          */
+/* bearings: everything 0), SFM_RELPOSE_NO_MODEL (not kept: everything 0 but */
+/* iterations and min_nfa, the best seen, +inf when none),                   */
+/* SFM_RELPOSE_AMBIGUOUS (E, error_max, min_nfa, n_inliers and the inliers   */
+/* kept; the vote did not single out a motion: pose, n_front and             */
+/* angle_median 0), SFM_RELPOSE_OK.  E = +-[t]x R up to rounding.            */
+/* Two device runs give the same bits.  Host and device run the same         */
+/* statements on every number of the search; they differ in the last bits of */
+/* angle_median (atan2) only.                                                */
+/* ------------------------------------------------------------------------ */
+#define SFM_RELPOSE_OK        0
+#define SFM_RELPOSE_FEW       1
+#define SFM_RELPOSE_NO_MODEL  2
+#define SFM_RELPOSE_AMBIGUOUS 3
+typedef struct sfm_relpose_opts {
+    double  precision;        /* px, upper bound of the a-contrario threshold; <= 0 or +inf: none */
+    int32_t max_iterations;   /* 4096 (>= 1)                                                       */
+    int32_t reserved;
+    double  front_ratio;      /* 0.7: second-best / best cheirality count has to be below it       */
+} sfm_relpose_opts;
+typedef struct sfm_relpose_result {
+    double  E[9];           /* row-major, on bearings: b_J' E b_I = 0, Frobenius norm sqrt(2) */
+    double  pose[6];        /* angle-axis, then t, |t| = 1: P_J = R P_I + t                    */
+    double  error_max;      /* px: square root of the a-contrario threshold                    */
+    double  min_nfa;        /* log10 NFA of the best model                                     */
+    double  angle_median;   /* degrees                                                         */
+    int32_t n_inliers;
+    int32_t n_front;
+    int32_t iterations;     /* RANSAC iterations run                                           */
+    int32_t status;         /* SFM_RELPOSE_*                                                   */
+} sfm_relpose_result;
+/* [cpu] {4.0, 4096, 0, 0.7}; NULL opts below select them. */
+void sfm_relpose_default_options(sfm_relpose_opts* opts);
+/* inliers[off[q] + t], t < results[q].n_inliers: the inliers (indices into
+ * the problem's list) in ascending (error, index) order under E; the rest of
+ * inliers[] is left alone.  Every argument check runs on the host before any
+ * device call: a null pointer, negative counts, off[0] != 0 or off not
+ * monotone, an unknown camera_model, pair_intr outside [0, n_intr), a
+ * non-positive image size, max_iterations < 1 or a NaN precision or
+ * front_ratio: SFM_ERR_INVALID_ARG; n_pairs or off[n_pairs] >= 2^31, or a
+ * problem drawing more than 2^18 random numbers: SFM_ERR_UNSUPPORTED.
+ * Problems of any size (the sort moves from LDS to global memory above 8192
+ * correspondences).  It does not shard.  A context created with
+ * SFM_CTX_TIME_KERNELS reports the kernel's device time through
+ * sfm_ctx_last_kernel_ms. */
+int sfm_relpose(sfm_ctx* ctx, int32_t camera_model, int64_t n_pairs, const int64_t* off /* [n_pairs+1] */,
+                const double* xy /* [4*n] */, const int32_t* pair_intr /* [2*n_pairs] */,
+                const double* intr /* [iw*n_intr] */, int32_t n_intr, const int32_t* wh /* [4*n_pairs] */,
+                const sfm_relpose_opts* opts, sfm_relpose_result* results /* [n_pairs] */, int32_t* inliers /* [n] */);
+/* [cpu] The same on the host, a serial loop over the same statements. */
+int sfm_relpose_host(int32_t camera_model, int64_t n_pairs, const int64_t* off, const double* xy,
+                     const int32_t* pair_intr, const double* intr, int32_t n_intr, const int32_t* wh,
+                     const sfm_relpose_opts* opts, sfm_relpose_result* results, int32_t* inliers);
+/* [cpu] The minimal solver alone: unit bearings bI[3i..], bJ[3i..], i < 5;
+ * *n models, model m = E[m][0..8] row-major. */
+int sfm_relpose_5pt(const double bI[15], const double bJ[15], double E[10][9], int32_t* n);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
