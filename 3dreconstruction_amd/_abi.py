@@ -258,6 +258,17 @@ class RelposeResult(C.Structure):
                 ("n_front", C.c_int32), ("iterations", C.c_int32), ("status", C.c_int32)]
 
 
+class SiftOptions(C.Structure):
+    _fields_ = [("n_octaves", C.c_int32), ("n_scales", C.c_int32), ("first_octave", C.c_int32),
+                ("edge_threshold", C.c_float), ("peak_threshold", C.c_float), ("root_sift", C.c_int32),
+                ("orientation", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SiftSummary(C.Structure):
+    _fields_ = [("n_images", C.c_int64), ("n_keypoints", C.c_int64), ("n_features", C.c_int64),
+                ("n_written", C.c_int64), ("n_overflow", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 class SparseFilterStats(C.Structure):
     _fields_ = [("n_pairs_in", C.c_int64), ("n_pairs_out", C.c_int64), ("n_matches_in", C.c_int64),
                 ("n_matches_out", C.c_int64)]
@@ -336,6 +347,14 @@ SIGNATURES = [
     ("sfm_relpose_host", C.c_int, [C.c_int32, C.c_int64, i64p, f64p, i32p, f64p, C.c_int32, i32p,
                                    C.POINTER(RelposeOpts), C.POINTER(RelposeResult), i32p]),
     ("sfm_relpose_5pt", C.c_int, [f64p, f64p, f64p, i32p]),
+    ("sfm_sift_options_default", None, [C.POINTER(SiftOptions)]),
+    ("sfm_sift", C.c_int, [C.c_void_p, u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
+                           f32p, u8p, i64p, C.POINTER(SiftSummary)]),
+    ("sfm_sift_host", C.c_int, [u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
+                                f32p, u8p, i64p, C.POINTER(SiftSummary)]),
+    ("sfm_synth_image", C.c_int, [C.c_int32, C.c_int32, C.c_uint64, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, u8p]),
+    ("sfm_mvg_write_feat", C.c_int, [C.c_char_p, f32p, C.c_int64]),
     ("sfm_ba_intr_width", C.c_int, [C.c_int32]),
     ("sfm_ba_partition", C.c_int, [C.POINTER(BAProblem), C.c_int32, i64p, i64p]),
     ("sfm_ba_describe", C.c_int, [C.POINTER(BAProblem), C.c_int32, C.c_int32, C.POINTER(BAPlanShape)]),

@@ -571,6 +571,51 @@ def relpose_5pt(bI, bJ):
     return [E[9 * m:9 * m + 9].reshape(3, 3).copy() for m in range(n.value)]
 
 
+def sift_default_options():
+    o = abi.SiftOptions()
+    abi.load().sfm_sift_options_default(C.byref(o))
+    return o
+
+
+def sift(ctx, gray, opts=None, cap_per_img=8192):
+    """sfm_sift (ctx None: sfm_sift_host, on the CPU) over gray (n_img, h, w)
+    uint8 images of one size.  Returns ([(xyso (n, 4) float32, desc (n, 128)
+    uint8), ...] per image, holding min(n_feat, cap_per_img) rows, n_feat
+    (n_img,) int64 the true counts, and the summary as a dict."""
+    g = np.ascontiguousarray(gray, np.uint8)
+    if g.ndim == 2:
+        g = g[None]
+    n_img, h, w = g.shape
+    cap = int(cap_per_img)
+    xyso = np.zeros((max(n_img, 1), max(cap, 1), 4), np.float32)
+    desc = np.zeros((max(n_img, 1), max(cap, 1), 128), np.uint8)
+    n_feat = np.zeros(max(n_img, 1), np.int64)
+    sm = abi.SiftSummary()
+    args = (abi.ptr(g, abi.u8p), n_img, w, h, C.byref(opts) if opts is not None else None, cap,
+            abi.ptr(xyso, abi.f32p) if cap else None, abi.ptr(desc, abi.u8p) if cap else None,
+            abi.ptr(n_feat, abi.i64p), C.byref(sm))
+    if ctx is None:
+        _check(abi.load().sfm_sift_host(*args), "sfm_sift_host")
+    else:
+        _check(ctx.lib.sfm_sift(ctx.h, *args), "sfm_sift")
+    n_feat = n_feat[:n_img]
+    out = [(xyso[i, :min(int(n_feat[i]), cap)].copy(), desc[i, :min(int(n_feat[i]), cap)].copy())
+           for i in range(n_img)]
+    return out, n_feat, {f: getattr(sm, f) for f, _ in abi.SiftSummary._fields_}
+
+
+def synth_image(w, h, seed, angle=0.0, tx=0.0, ty=0.0, scale=1.0):
+    """sfm_synth_image: the (h, w) uint8 blob-field view the golden SIFT fixtures were taken from."""
+    g = np.zeros((h, w), np.uint8)
+    _check(abi.load().sfm_synth_image(w, h, seed, angle, tx, ty, scale, abi.ptr(g, abi.u8p)), "sfm_synth_image")
+    return g
+
+
+def mvg_write_feat(path, xyso):
+    f = np.ascontiguousarray(xyso, np.float32).reshape(-1, 4)
+    _check(abi.load().sfm_mvg_write_feat(_b(path), abi.ptr(f, abi.f32p), f.shape[0]), "sfm_mvg_write_feat")
+
+
 def tracks_default_options():
     o = abi.TracksOpts()
     abi.load().sfm_tracks_default_options(C.byref(o))

@@ -596,6 +596,22 @@ extern "C" int sfm_mvg_read_feat(const char* path, float* xyso, int64_t cap_rows
     });
 }
 
+extern "C" int sfm_mvg_write_feat(const char* path, const float* xyso, int64_t n_rows) {
+    return guarded([&] {
+        SFM_REQUIRE(path && (xyso || n_rows == 0) && n_rows >= 0, SFM_ERR_INVALID_ARG, "bad argument");
+        std::FILE* f = std::fopen(path, "w");
+        SFM_REQUIRE(f, SFM_ERR_INVALID_ARG, "cannot write %s", path);
+        bool ok = true;
+        // nine significant digits: sfm_mvg_read_feat gets the same floats back
+        for (int64_t i = 0; i < n_rows && ok; ++i)
+            ok = std::fprintf(f, "%.9g %.9g %.9g %.9g\n", (double)xyso[4 * i], (double)xyso[4 * i + 1],
+                              (double)xyso[4 * i + 2], (double)xyso[4 * i + 3]) > 0;
+        ok = (std::fclose(f) == 0) && ok;
+        SFM_REQUIRE(ok, SFM_ERR_INVALID_ARG, "write failed: %s", path);
+        return SFM_OK;
+    });
+}
+
 extern "C" int sfm_mvg_load_pairs(const char* path, int32_t n_views, int32_t* pairs, int64_t cap, int64_t* n_pairs) {
     return guarded([&] {
         SFM_REQUIRE(path && n_pairs && n_views >= 0, SFM_ERR_INVALID_ARG, "bad argument");

@@ -408,3 +408,50 @@ extern "C" int sfm_synth_orbit_image(const sfm_synth_orbit_config* cfg, int32_t 
     }
     return SFM_OK;
 }
+
+// ---- gray test images ------------------------------------------------------------
+// The blob field of oracle/vlsift_tool.c: 900 anisotropic Gaussian blobs on a
+// mid-gray ground, drawn from mix64 of (seed, index), seen through a rotated,
+// scaled and shifted view and quantised to 8 bits.  The golden SIFT fixtures
+// of tests/golden/ were extracted from these images, so a test can rebuild the
+// input of a fixture on any machine.
+namespace {
+inline uint64_t img_mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+inline double img_uni(uint64_t seed, uint64_t k) {
+    return (double)(img_mix64(seed + 0x9E3779B97F4A7C15ULL * (k + 1)) >> 11) * 0x1.0p-53;
+}
+}  // namespace
+
+extern "C" int sfm_synth_image(int32_t w, int32_t h, uint64_t seed, double angle, double tx, double ty, double scale,
+                               uint8_t* gray) {
+    if (w <= 0 || h <= 0 || !gray || !(scale > 0)) return SFM_ERR_INVALID_ARG;
+    constexpr int kBlobs = 900;
+    std::vector<double> bx(kBlobs), by(kBlobs), bs(kBlobs), ba(kBlobs), be(kBlobs);
+    for (int i = 0; i < kBlobs; ++i) {
+        bx[i] = img_uni(seed, 5 * i) * w * 1.2 - 0.1 * w;
+        by[i] = img_uni(seed, 5 * i + 1) * h * 1.2 - 0.1 * h;
+        bs[i] = 2.0 + 14.0 * img_uni(seed, 5 * i + 2);
+        ba[i] = (img_uni(seed, 5 * i + 3) - 0.5) * 220.0;
+        be[i] = 0.4 + 1.6 * img_uni(seed, 5 * i + 4);
+    }
+    // image(u, v) = field(A^-1 ((u, v) - c - t) + c)
+    const double ca = std::cos(angle) / scale, sa = std::sin(angle) / scale, cx = 0.5 * w, cy = 0.5 * h;
+    for (int v = 0; v < h; ++v)
+        for (int u = 0; u < w; ++u) {
+            const double du = u - cx - tx, dv = v - cy - ty;
+            const double x = ca * du + sa * dv + cx, y = -sa * du + ca * dv + cy;
+            double f = 110.0;
+            for (int i = 0; i < kBlobs; ++i) {
+                const double dx = x - bx[i], dy = y - by[i];
+                const double r2 = (dx * dx + be[i] * dy * dy) / (bs[i] * bs[i]);
+                if (r2 < 16.0) f += ba[i] * std::exp(-0.5 * r2);
+            }
+            f = f < 0 ? 0 : (f > 255 ? 255 : f);
+            gray[(size_t)v * w + u] = (uint8_t)(f + 0.5);
+        }
+    return SFM_OK;
+}

@@ -11,6 +11,9 @@
 //   RelativePoser         the relative pose of image pairs from their matches and
 //                         the engine's choice of the initial pair
 //                         (relative_pose.hpp; sfm_relpose)
+//   SIFT_Image_describer  src/nonFree/sift/SIFT_describer.hpp and detectFeature()
+//                         (sparseBuilder.cpp:575-756) on 8-bit gray buffers
+//                         (sift.hpp; sfm_sift)
 //   TracksBuilder         OpenMVG's tracks::TracksBuilder, the first step of the
 //                         engine reconstruction() runs (sparseBuilder.cpp:1474-1508):
 //                         pairwise matches into tracks (tracks.hpp; sfm_tracks_build)
@@ -40,6 +43,7 @@
 #include "frames.hpp"
 #include "localizer.hpp"
 #include "relative_pose.hpp"
+#include "sift.hpp"
 #include "tracks.hpp"
 #include "triangulator.hpp"
 #include "world.hpp"
@@ -186,6 +190,25 @@ class RelativePoser : public BasicRelativePoser<GpuRelposeBackend> {
    public:
     explicit RelativePoser(Context& ctx = Context::thread_default())
         : BasicRelativePoser<GpuRelposeBackend>(GpuRelposeBackend{&ctx}) {}
+};
+
+// ---------------------------------------------------------------------------
+// SIFT_Image_describer (sift.hpp) on the GPU: sfm_sift
+// ---------------------------------------------------------------------------
+struct GpuSiftBackend {
+    Context* ctx;
+    int sift(const uint8_t* gray, int32_t n_img, int32_t w, int32_t h, const sfm_sift_options& o, int64_t cap,
+             float* xyso, uint8_t* desc, int64_t* n_feat, sfm_sift_summary* sm) const {
+        return sfm_sift(ctx->get(), gray, n_img, w, h, &o, cap, xyso, desc, n_feat, sm);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+class SIFT_Image_describer : public BasicSiftDescriber<GpuSiftBackend> {
+   public:
+    explicit SIFT_Image_describer(const Params& params = Params(), bool bOrientation = true,
+                                  Context& ctx = Context::thread_default())
+        : BasicSiftDescriber<GpuSiftBackend>(GpuSiftBackend{&ctx}, params, bOrientation) {}
 };
 
 // ---------------------------------------------------------------------------

@@ -12,7 +12,7 @@ HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/
 
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
-     tests/cpp/relpose_test
+     tests/cpp/relpose_test tests/cpp/sift_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -73,4 +73,10 @@ tests/cpp/resect_test: tests/cpp/resect_test.cpp $(CSRC)/resect.cpp $(HDRS)
 # sfm::RelativePoser on the host backend: csrc/relpose.cpp's host path compiled
 # in (no library, no HIP runtime: host only)
 tests/cpp/relpose_test: tests/cpp/relpose_test.cpp $(CSRC)/relpose.cpp $(HDRS)
+	g++ -O2 -std=c++17 -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $<
+
+# sfm::HostSIFT_Image_describer and detectFeature(): csrc/sift.cpp's host path,
+# the image generator and the file formats compiled in (no library, no HIP
+# runtime: host only)
+tests/cpp/sift_test: tests/cpp/sift_test.cpp $(CSRC)/sift.cpp $(CSRC)/synth.cpp $(CSRC)/mvg_io.cpp $(HDRS)
 	g++ -O2 -std=c++17 -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $<

@@ -476,6 +476,13 @@ int sfm_exhaustive_pairs(int32_t n_img, int32_t* pairs);
  * their neighbours (true correspondences) plus integer noise. */
 int sfm_synth_descriptors(int32_t n_img, int32_t n_kp, uint64_t seed,
                           uint8_t* desc /* [n_img*n_kp*128] */);
+/* [cpu] Deterministic gray test image, w x h bytes: 900 Gaussian blobs drawn
+ * from (seed, index) on a mid-gray ground, seen rotated by angle about the
+ * centre, scaled and shifted by (tx, ty), so that views of one seed share true
+ * correspondences.  The generator of the golden SIFT fixtures (tests/golden,
+ * oracle/vlsift_tool.c), restated. */
+int sfm_synth_image(int32_t w, int32_t h, uint64_t seed, double angle, double tx, double ty, double scale,
+                    uint8_t* gray /* [w*h] */);
 
 /* ------------------------------------------------------------------------ */
 /* Incremental loop: SequentialActuator (src/actuator/SequentialActuator.h)  */
@@ -606,6 +613,8 @@ int sfm_mvg_read_desc(const char* path, uint8_t* desc, int64_t cap_rows, int64_t
 int sfm_mvg_write_desc(const char* path, const uint8_t* desc, int64_t n_rows);
 /* [cpu] <stem>.feat: text "x y scale orientation" per keypoint (SIOPointFeature). */
 int sfm_mvg_read_feat(const char* path, float* xyso /* [4*n] */, int64_t cap_rows, int64_t* n_rows);
+/* nine significant digits per number, so that reading gives the same floats back */
+int sfm_mvg_write_feat(const char* path, const float* xyso /* [4*n] */, int64_t n_rows);
 /* [cpu] pairs.bin (text despite its name): loadPairs(N, ...) / savePairs
  * (:801, :948): lines "I J1 J2 ...", stored as sorted unique (min, max). */
 int sfm_mvg_load_pairs(const char* path, int32_t n_views, int32_t* pairs, int64_t cap,
@@ -1185,6 +1194,89 @@ int sfm_relpose_host(int32_t camera_model, int64_t n_pairs, const int64_t* off, 
 /* [cpu] The minimal solver alone: unit bearings bI[3i..], bJ[3i..], i < 5;
  * *n models, model m = E[m][0..8] row-major. */
 int sfm_relpose_5pt(const double bI[15], const double bJ[15], double E[10][9], int32_t* n);
+
+/* ------------------------------------------------------------------------ */
+/* SIFT extraction: detect, orient and describe               */
+/*                                                                           */
+/* The first stage of the sparse pipeline: sparseBuilder::detectFeature()'s  */
+/* SIFT_Image_describer over VLFeat's sift, on a batch of 8-bit gray images  */
+/* of one size.  Image decoding stays outside: the input is gray bytes.      */
+/*   scale space  first octave at the image's size (first_octave 0), then    */
+/*             halved n_octaves - 1 times (every other pixel of level S);    */
+/*             octaves run while both sides are at least 3.  Levels s = -1   */
+/*             .. S+1 per octave, sigma0 = 1.6 * 2^(1/S), input blur 0.5;    */
+/*             each level is the one below smoothed by a separable Gaussian  */
+/*             of sqrt(sigma_s^2 - sigma_{s-1}^2), half-width ceil(4 sigma), */
+/*             the border continued, columns first, float, taps added in     */
+/*             order.  The taps are computed once on the host.               */
+/*   detection    strict 3x3x3 extrema of the DoG at or beyond 0.8 peak,     */
+/*             peak = 255 * peak_threshold / S; up to five steps of the 3-D  */
+/*             quadratic fit (the cell moves when an offset passes 0.6);     */
+/*             kept with |value| > peak, edge score below (e+1)^2 / e, every */
+/*             offset below 1.5 and the point inside the octave.             */
+/*   orientation  36 bins over a Gaussian window of 1.5 sigma, linear in the */
+/*             angle, six 3-box passes, peaks at or above 0.8 of the largest */
+/*             refined by a parabola, at most four, in bin order.            */
+/*             orientation = 0: one upright feature (angle 0) per keypoint.  */
+/*   descriptor   4x4x8 bins, magnification 3, window 2, trilinear; unit     */
+/*             length, clamp at 0.2, unit length; then root_sift:            */
+/*             (uint8)(512 sqrt(d / sum d)), else (uint8)(512 d).  A feature */
+/*             whose centre rounds onto the last row of its octave gets a    */
+/*             zero descriptor (the reference leaves its buffer as it was).  */
+/*   arithmetic   gradient magnitude and angle and the two Gaussian windows  */
+/*             use VLFeat's table / bit-trick replacements of sqrt, atan2    */
+/*             and exp, restated as plain arithmetic (csrc/sift_point.h), so */
+/*             host and device agree bit for bit; 2^x, sin and cos are short */
+/*             Taylor sums.                                                  */
+/* Features come in the reference's order: octave, then level, then row,     */
+/* then column of the extremum cell, then orientations in bin order.  A      */
+/* feature is (x, y, sigma, angle) in full-resolution pixels, float.         */
+/* Limits: first_octave != 0 (the ULTRA preset's upsampling) and masks are   */
+/* SFM_ERR_UNSUPPORTED / absent; n_scales <= 8; a Gaussian half-width above  */
+/* 32 is SFM_ERR_UNSUPPORTED.                                                */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_sift_options {
+    int32_t n_octaves;       /* 6                                             */
+    int32_t n_scales;        /* 3 (S)                                         */
+    int32_t first_octave;    /* 0; anything else: SFM_ERR_UNSUPPORTED         */
+    float   edge_threshold;  /* 10                                            */
+    float   peak_threshold;  /* 0.04 (NORMAL preset); HIGH: 0.01              */
+    int32_t root_sift;       /* 1                                             */
+    int32_t orientation;     /* 1                                             */
+    int32_t reserved;
+} sfm_sift_options;
+typedef struct sfm_sift_summary {
+    int64_t n_images;
+    int64_t n_keypoints;     /* refined keypoints, before orientations        */
+    int64_t n_features;      /* sum of n_feat                                 */
+    int64_t n_written;       /* rows written: sum of min(n_feat, cap_per_img) */
+    int64_t n_overflow;      /* images with n_feat > cap_per_img              */
+    double  kernel_ms;       /* device time of the kernels; -1 without        */
+                             /* SFM_CTX_TIME_KERNELS and on the host          */
+} sfm_sift_summary;
+/* [cpu] {6, 3, 0, 10, 0.04, 1, 1, 0}; NULL opts below select them. */
+void sfm_sift_options_default(sfm_sift_options* opts);
+/* gray: n_img images of w x h bytes, row-major, back to back.  Image i's
+ * features go to xyso[i][0 .. ][4] and desc[i][0 .. ][128] in canonical order,
+ * at most cap_per_img rows of them; n_feat[i] is always the true count, so
+ * n_feat[i] > cap_per_img says that image i was cut short.  That is not an
+ * error: the call returns SFM_OK and summary->n_overflow counts such images
+ * (cap_per_img 0 with null xyso / desc is the size query).  Rows past the
+ * count are left alone.  Every argument check runs on the host before any
+ * device call: a null pointer, a negative count, a non-positive image size,
+ * n_octaves < 0, n_scales < 1, edge_threshold <= 0 or peak_threshold < 0:
+ * SFM_ERR_INVALID_ARG; the limits above, more than 2^28 pixels per image or
+ * 65535 images: SFM_ERR_UNSUPPORTED.  n_img 0 and images smaller than 3 x 3
+ * give no features.  Two device runs, and device and host, give the same bits.
+ * It does not shard.  summary may be NULL.  A context created with
+ * SFM_CTX_TIME_KERNELS also reports the kernels' device time through
+ * sfm_ctx_last_kernel_ms. */
+int sfm_sift(sfm_ctx* ctx, const uint8_t* gray, int32_t n_img, int32_t w, int32_t h, const sfm_sift_options* opts,
+             int64_t cap_per_img, float* xyso /* [n_img][cap][4] */, uint8_t* desc /* [n_img][cap][128] */,
+             int64_t* n_feat /* [n_img] */, sfm_sift_summary* summary);
+/* [cpu] The same on the host, a serial loop over the same statements. */
+int sfm_sift_host(const uint8_t* gray, int32_t n_img, int32_t w, int32_t h, const sfm_sift_options* opts,
+                  int64_t cap_per_img, float* xyso, uint8_t* desc, int64_t* n_feat, sfm_sift_summary* summary);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
