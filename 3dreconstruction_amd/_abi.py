@@ -269,6 +269,37 @@ class SiftSummary(C.Structure):
                 ("n_written", C.c_int64), ("n_overflow", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+SFM_RECON_NEW, SFM_RECON_SOLVED = 0, 1
+SFM_RECON_OK, SFM_RECON_NO_INITIAL_PAIR = 0, 1
+
+
+class ReconOpts(C.Structure):
+    _fields_ = [("relpose", RelposeOpts), ("resect", ResectOpts), ("tri", TriOpts), ("ba", BAOptions),
+                ("wash", BAWashOpts), ("initial_pair", C.c_int32 * 2), ("pair_min_inliers", C.c_int32),
+                ("adjust", C.c_int32), ("pair_min_angle_deg", C.c_double), ("group_ratio", C.c_double),
+                ("wash_repeat_above", C.c_int32), ("max_adjust_repeats", C.c_int32),
+                ("min_track_len", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ReconCand(C.Structure):
+    _fields_ = [("round", C.c_int32), ("image", C.c_int32), ("count", C.c_int32), ("status", C.c_int32),
+                ("n_inliers", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ReconRound(C.Structure):
+    _fields_ = [("first_cand", C.c_int32), ("n_cand", C.c_int32), ("n_registered", C.c_int32),
+                ("adjust_repeats", C.c_int32), ("points_added", C.c_int64), ("obs_dropped", C.c_int64),
+                ("points_removed", C.c_int64), ("ba_rc", C.c_int32), ("reserved", C.c_int32),
+                ("ba", BASummary), ("wash", BAWashStats)]
+
+
+class ReconStats(C.Structure):
+    _fields_ = [("status", C.c_int32), ("initial_pair", C.c_int32 * 2), ("n_rounds", C.c_int32),
+                ("n_cands", C.c_int32), ("n_registered", C.c_int32), ("n_points", C.c_int64),
+                ("n_obs_kept", C.c_int64), ("final_removed", C.c_int64), ("final_adjust", ReconRound),
+                ("seconds", C.c_double * 8)]
+
+
 class SparseFilterStats(C.Structure):
     _fields_ = [("n_pairs_in", C.c_int64), ("n_pairs_out", C.c_int64), ("n_matches_in", C.c_int64),
                 ("n_matches_out", C.c_int64)]
@@ -347,6 +378,23 @@ SIGNATURES = [
     ("sfm_relpose_host", C.c_int, [C.c_int32, C.c_int64, i64p, f64p, i32p, f64p, C.c_int32, i32p,
                                    C.POINTER(RelposeOpts), C.POINTER(RelposeResult), i32p]),
     ("sfm_relpose_5pt", C.c_int, [f64p, f64p, f64p, i32p]),
+    ("sfm_recon_tracks_create", C.c_int, [C.c_void_p, C.POINTER(BAProblem), C.POINTER(C.c_void_p)]),
+    ("sfm_recon_tracks_create_host", C.c_int, [C.POINTER(BAProblem), C.POINTER(C.c_void_p)]),
+    ("sfm_recon_tracks_destroy", C.c_int, [C.c_void_p]),
+    ("sfm_recon_tracks_drop_obs", C.c_int, [C.c_void_p, i64p, C.c_int64]),
+    ("sfm_recon_visibility", C.c_int, [C.c_void_p, u8p, i32p]),
+    ("sfm_recon_gather", C.c_int, [C.c_void_p, f64p, u8p, i32p, C.c_int32, i64p, f64p, f64p, i64p, C.c_int64]),
+    ("sfm_recon_select", C.c_int, [C.c_void_p, u8p, u8p, C.c_int32, C.c_int32, i64p, i64p, i64p, i32p, f64p,
+                                   i64p, i64p, C.c_int64, C.c_int64]),
+    ("sfm_recon_default_options", None, [C.POINTER(ReconOpts)]),
+    ("sfm_reconstruct", C.c_int, [C.c_void_p, C.POINTER(BAProblem), f64p, i32p, i32p, C.c_int64,
+                                  C.POINTER(ReconOpts), f64p, f64p, u8p, u8p, u8p, C.POINTER(ReconRound),
+                                  C.c_int32, C.POINTER(ReconCand), C.c_int32, C.POINTER(ReconStats)]),
+    ("sfm_reconstruct_host", C.c_int, [C.POINTER(BAProblem), f64p, i32p, i32p, C.c_int64,
+                                       C.POINTER(ReconOpts), f64p, f64p, u8p, u8p, u8p, C.POINTER(ReconRound),
+                                       C.c_int32, C.POINTER(ReconCand), C.c_int32, C.POINTER(ReconStats)]),
+    ("sfm_sparse_reconstruct", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_double, C.POINTER(ReconOpts),
+                                         C.POINTER(ReconStats)]),
     ("sfm_sift_options_default", None, [C.POINTER(SiftOptions)]),
     ("sfm_sift", C.c_int, [C.c_void_p, u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
                            f32p, u8p, i64p, C.POINTER(SiftSummary)]),

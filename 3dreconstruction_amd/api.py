@@ -1082,3 +1082,143 @@ def sparse_filter(ctx, matches_dir, opts=None):
     _check(lib.sfm_sparse_filter(ctx.h, _b(matches_dir), C.byref(opts or fmatrix_opts()), C.byref(st)),
            "sfm_sparse_filter")
     return st
+
+
+# ---- incremental reconstruction -----------------------------------------------------
+def recon_default_options():
+    o = abi.ReconOpts()
+    abi.load().sfm_recon_default_options(C.byref(o))
+    return o
+
+
+class ReconTracks:
+    """sfm_recon_tracks: a problem's tracks held resident (ctx None: the host
+    twin) for the three round queries.  Every query returns what the device or
+    the host walk wrote, compacted, as numpy arrays."""
+
+    def __init__(self, ctx, problem):
+        self.lib = abi.load()
+        self.n_img, self.n_pt, self.n_obs = problem.n_img, problem.n_pt, problem.n_obs
+        # the rows a gather of an image can have at most
+        img = np.ctypeslib.as_array(problem.obs_img, shape=(max(self.n_obs, 1),))[:self.n_obs]
+        self._per_img = np.bincount(img, minlength=max(self.n_img, 1)) if self.n_obs else np.zeros(max(self.n_img, 1), int)
+        h = C.c_void_p()
+        if ctx is None:
+            _check(self.lib.sfm_recon_tracks_create_host(C.byref(problem), C.byref(h)), "sfm_recon_tracks_create_host")
+        else:
+            _check(self.lib.sfm_recon_tracks_create(ctx.h, C.byref(problem), C.byref(h)), "sfm_recon_tracks_create")
+            ctx._adopt(self)
+        self.h = h
+
+    def _ok(self, pt_ok):
+        a = np.ascontiguousarray(np.asarray(pt_ok).astype(np.uint8).reshape(-1))
+        assert len(a) == self.n_pt
+        return a if self.n_pt else np.zeros(1, np.uint8)
+
+    def drop_obs(self, obs):
+        obs = np.ascontiguousarray(np.asarray(obs, np.int64).reshape(-1))
+        _check(self.lib.sfm_recon_tracks_drop_obs(self.h, abi.ptr(obs, abi.i64p), len(obs)), "sfm_recon_tracks_drop_obs")
+
+    def visibility(self, pt_ok):
+        count = np.zeros(max(self.n_img, 1), np.int32)
+        _check(self.lib.sfm_recon_visibility(self.h, abi.ptr(self._ok(pt_ok), abi.u8p), abi.ptr(count, abi.i32p)),
+               "sfm_recon_visibility")
+        return count[:self.n_img]
+
+    def gather(self, X, pt_ok, images):
+        """(off [n_images + 1], X3 [n, 3], uv [n, 2], obs [n])"""
+        images = np.ascontiguousarray(np.asarray(images, np.int32).reshape(-1))
+        X = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+        if not len(X):
+            X = np.zeros(3)
+        off = np.zeros(len(images) + 1, np.int64)
+        ok_img = images[(images >= 0) & (images < self.n_img)]
+        cap = int(self._per_img[ok_img].sum()) if len(ok_img) else 0
+        X3 = np.zeros((max(cap, 1), 3))
+        uv = np.zeros((max(cap, 1), 2))
+        obs = np.zeros(max(cap, 1), np.int64)
+        _check(self.lib.sfm_recon_gather(self.h, abi.ptr(X, abi.f64p), abi.ptr(self._ok(pt_ok), abi.u8p),
+                                         abi.ptr(images, abi.i32p), len(images), abi.ptr(off, abi.i64p),
+                                         abi.ptr(X3, abi.f64p), abi.ptr(uv, abi.f64p), abi.ptr(obs, abi.i64p), cap),
+               "sfm_recon_gather")
+        return off, X3[:off[-1]].copy(), uv[:off[-1]].copy(), obs[:off[-1]].copy()
+
+    def select(self, registered, pt_ok, mode, min_track_len=2):
+        """dict(pt_offsets, obs_img, obs_uv [n, 2], pt_map, obs_map)"""
+        reg = np.ascontiguousarray(np.asarray(registered).astype(np.uint8).reshape(-1))
+        assert len(reg) == self.n_img
+        if not self.n_img:
+            reg = np.zeros(1, np.uint8)
+        n_pt, n_obs = C.c_int64(), C.c_int64()
+        off = np.zeros(self.n_pt + 1, np.int64)
+        img = np.zeros(max(self.n_obs, 1), np.int32)
+        uv = np.zeros((max(self.n_obs, 1), 2))
+        pm = np.zeros(max(self.n_pt, 1), np.int64)
+        om = np.zeros(max(self.n_obs, 1), np.int64)
+        _check(self.lib.sfm_recon_select(self.h, abi.ptr(reg, abi.u8p), abi.ptr(self._ok(pt_ok), abi.u8p), mode,
+                                         min_track_len, C.byref(n_pt), C.byref(n_obs), abi.ptr(off, abi.i64p),
+                                         abi.ptr(img, abi.i32p), abi.ptr(uv, abi.f64p), abi.ptr(pm, abi.i64p),
+                                         abi.ptr(om, abi.i64p), self.n_pt, self.n_obs), "sfm_recon_select")
+        n_pt, n_obs = n_pt.value, n_obs.value
+        return dict(pt_offsets=off[:n_pt + 1].copy(), obs_img=img[:n_obs].copy(), obs_uv=uv[:n_obs].copy(),
+                    pt_map=pm[:n_pt].copy(), obs_map=om[:n_obs].copy())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.sfm_recon_tracks_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _struct_dict(s):
+    out = {}
+    for f, t in s._fields_:
+        v = getattr(s, f)
+        out[f] = _struct_dict(v) if isinstance(v, C.Structure) else (list(v) if isinstance(v, C.Array) else v)
+    return out
+
+
+def reconstruct(ctx, problem, intr, wh, pairs, opts=None, cap_rounds=256, cap_cands=1024):
+    """sfm_reconstruct (ctx None: sfm_reconstruct_host, on the CPU) over the
+    tracks of `problem`: dict(rc, extr [n_img, 6], intr (refined copy),
+    X [n_pt, 3], registered, pt_ok, keep_obs (bool), rounds, cands (lists of
+    dicts, what fitted the capacities), stats (dict))."""
+    lib = abi.load()
+    n_img, n_pt, n_obs = problem.n_img, problem.n_pt, problem.n_obs
+    intr = np.ascontiguousarray(np.asarray(intr, np.float64).reshape(-1)).copy()
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1))
+    assert len(wh) == 2 * n_img
+    extr = np.zeros(6 * max(n_img, 1))
+    X = np.zeros(3 * max(n_pt, 1))
+    reg = np.zeros(max(n_img, 1), np.uint8)
+    ok = np.zeros(max(n_pt, 1), np.uint8)
+    keep = np.zeros(max(n_obs, 1), np.uint8)
+    rounds = (abi.ReconRound * max(cap_rounds, 1))()
+    cands = (abi.ReconCand * max(cap_cands, 1))()
+    st = abi.ReconStats()
+    args = (C.byref(problem), abi.ptr(intr, abi.f64p), abi.ptr(wh, abi.i32p), abi.ptr(pairs, abi.i32p), len(pairs) // 2,
+            C.byref(opts) if opts is not None else None, abi.ptr(extr, abi.f64p), abi.ptr(X, abi.f64p),
+            abi.ptr(reg, abi.u8p), abi.ptr(ok, abi.u8p), abi.ptr(keep, abi.u8p), rounds, cap_rounds, cands, cap_cands,
+            C.byref(st))
+    rc = lib.sfm_reconstruct_host(*args) if ctx is None else lib.sfm_reconstruct(ctx.h, *args)
+    _check(rc, "sfm_reconstruct_host" if ctx is None else "sfm_reconstruct")
+    return dict(rc=rc, extr=extr[:6 * n_img].reshape(-1, 6), intr=intr, X=X[:3 * n_pt].reshape(-1, 3),
+                registered=reg[:n_img].astype(bool), pt_ok=ok[:n_pt].astype(bool), keep_obs=keep[:n_obs].astype(bool),
+                rounds=[_struct_dict(rounds[k]) for k in range(min(st.n_rounds, cap_rounds))],
+                cands=[_struct_dict(cands[k]) for k in range(min(st.n_cands, cap_cands))], stats=_struct_dict(st))
+
+
+def sparse_reconstruct(ctx, matches_dir, out_dir, focal=-1.0, opts=None):
+    """sfm_sparse_reconstruct: sparseBuilder::reconstruction(), file-staged;
+    writes <out_dir>/cloud_and_poses.ply and returns the stats dict."""
+    st = abi.ReconStats()
+    _check(abi.load().sfm_sparse_reconstruct(ctx.h, _b(matches_dir), _b(out_dir), focal,
+                                             C.byref(opts) if opts is not None else None, C.byref(st)),
+           "sfm_sparse_reconstruct")
+    return _struct_dict(st)

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../../include/sfmcore.h"
+#include "../../csrc/relpose_best.h"
 #include "world.hpp"
 
 namespace sfm {
@@ -103,13 +104,7 @@ class BasicRelativePoser {
     // angle_median above min_angle_deg, the one with the largest angle_median
     // (the first on a tie); -1 when there is none.
     int64_t best(int32_t min_inliers = 100, double min_angle_deg = 3.0) const {
-        int64_t b = -1;
-        for (int64_t q = 0; q < (int64_t)results_.size(); ++q) {
-            const sfm_relpose_result& r = results_[q];
-            if (r.status != SFM_RELPOSE_OK || !(r.n_front > min_inliers) || !(r.angle_median > min_angle_deg)) continue;
-            if (b < 0 || r.angle_median > results_[b].angle_median) b = q;
-        }
-        return b;
+        return relpose_best(results_.data(), (int64_t)results_.size(), min_inliers, min_angle_deg);
     }
 
    private:

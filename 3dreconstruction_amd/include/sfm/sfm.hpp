@@ -11,6 +11,9 @@
 //   RelativePoser         the relative pose of image pairs from their matches and
 //                         the engine's choice of the initial pair
 //                         (relative_pose.hpp; sfm_relpose)
+//   SequentialSfMReconstructionEngine  OpenMVG's incremental engine over the
+//                         stages above (reconstruction.hpp; sfm_reconstruct), and
+//                         sparseBuilder::reconstruction() file-staged
 //   SIFT_Image_describer  src/nonFree/sift/SIFT_describer.hpp and detectFeature()
 //                         (sparseBuilder.cpp:575-756) on 8-bit gray buffers
 //                         (sift.hpp; sfm_sift)
@@ -42,6 +45,7 @@
 #include "adjuster.hpp"
 #include "frames.hpp"
 #include "localizer.hpp"
+#include "reconstruction.hpp"
 #include "relative_pose.hpp"
 #include "sift.hpp"
 #include "tracks.hpp"
@@ -193,6 +197,31 @@ class RelativePoser : public BasicRelativePoser<GpuRelposeBackend> {
 };
 
 // ---------------------------------------------------------------------------
+// SequentialSfMReconstructionEngine (reconstruction.hpp) on the GPU:
+// sfm_reconstruct
+// ---------------------------------------------------------------------------
+struct GpuReconBackend {
+    static constexpr bool adjusts = true;
+    Context* ctx;
+    int reconstruct(const sfm_ba_problem& tracks, double* intr, const int32_t* wh, const int32_t* pairs, int64_t n_pairs,
+                    const sfm_recon_opts& o, double* extr, double* X, uint8_t* registered, uint8_t* pt_ok,
+                    uint8_t* keep_obs, sfm_recon_round* rounds, int32_t cap_rounds, sfm_recon_cand* cands,
+                    int32_t cap_cands, sfm_recon_stats* stats) const {
+        return sfm_reconstruct(ctx->get(), &tracks, intr, wh, pairs, n_pairs, &o, extr, X, registered, pt_ok, keep_obs,
+                               rounds, cap_rounds, cands, cap_cands, stats);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+class SequentialSfMReconstructionEngine : public BasicSequentialSfMReconstructionEngine<GpuReconBackend> {
+   public:
+    SequentialSfMReconstructionEngine(WorldStructure::Ptr world, std::vector<Image::Ptr> images, int32_t width,
+                                      int32_t height, Context& ctx = Context::thread_default())
+        : BasicSequentialSfMReconstructionEngine<GpuReconBackend>(GpuReconBackend{&ctx}, std::move(world),
+                                                                  std::move(images), width, height) {}
+};
+
+// ---------------------------------------------------------------------------
 // SIFT_Image_describer (sift.hpp) on the GPU: sfm_sift
 // ---------------------------------------------------------------------------
 struct GpuSiftBackend {
@@ -310,6 +339,21 @@ class sparseBuilder {
     }
     const sfm_sparse_filter_stats& filterStats() const { return filter_stats_; }
 
+    // reconstruction() (:1283-1599) with its settings: engine INCREMENTAL,
+    // PINHOLE_CAMERA_RADIAL3, ADJUST_ALL, no initial pair given: sfm_data.json
+    // + <stem>.feat + matches.f.bin -> <base>/output/reconstruction/cloud_and_poses.ply
+    // (the directory has to exist).  focal <= 0: 1.2 * max(w, h).  sfm_data.bin
+    // is not written.
+    void reconstruction(double focal = -1.0, const std::string& out_dir = std::string()) {
+        const std::string out =
+            !out_dir.empty() ? out_dir
+            : matches_dir_.size() >= 7 ? matches_dir_.substr(0, matches_dir_.size() - 7) + "reconstruction"
+                                       : std::string(".");
+        last_rc_ = sfm_sparse_reconstruct(ctx_->get(), matches_dir_.c_str(), out.c_str(), focal, nullptr, &recon_stats_);
+        if (last_rc_ != SFM_OK) std::fprintf(stderr, "reconstruction failed: %s\n", sfm_last_error());
+    }
+    const sfm_recon_stats& reconstructionStats() const { return recon_stats_; }
+
     // in-memory regions: per view, n x 128 uint8 descriptors
     void setRegions(std::vector<std::vector<uint8_t>> regions) { regions_ = std::move(regions); }
     // exhaustivePairs(N) (:786)
@@ -359,6 +403,7 @@ class sparseBuilder {
     int last_rc_ = SFM_OK;
     sfm_sparse_match_stats stats_{};
     sfm_sparse_filter_stats filter_stats_{};
+    sfm_recon_stats recon_stats_{};
     std::vector<std::vector<uint8_t>> regions_;
 };
 

@@ -12,7 +12,7 @@ HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/
 
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
-     tests/cpp/relpose_test tests/cpp/sift_test
+     tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -80,3 +80,11 @@ tests/cpp/relpose_test: tests/cpp/relpose_test.cpp $(CSRC)/relpose.cpp $(HDRS)
 # runtime: host only)
 tests/cpp/sift_test: tests/cpp/sift_test.cpp $(CSRC)/sift.cpp $(CSRC)/synth.cpp $(CSRC)/mvg_io.cpp $(HDRS)
 	g++ -O2 -std=c++17 -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $<
+
+# sfm::SequentialSfMReconstructionEngine on the host backend: the host paths of
+# csrc/recon.cpp and of the stages it drives compiled in, one translation unit
+# each (no library, no HIP runtime: host only)
+RECON_HOST_SRCS := $(CSRC)/recon.cpp $(CSRC)/relpose.cpp $(CSRC)/resect.cpp $(CSRC)/tri.cpp
+RECON_HOST_DEFS := -DSFM_RECON_HOST_ONLY -DSFM_RELPOSE_HOST_ONLY -DSFM_RESECT_HOST_ONLY -DSFM_TRI_HOST_ONLY
+tests/cpp/recon_test: tests/cpp/recon_test.cpp $(RECON_HOST_SRCS) $(HDRS)
+	g++ -O2 -std=c++17 -w $(RECON_HOST_DEFS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(RECON_HOST_SRCS)

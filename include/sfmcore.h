@@ -1278,6 +1278,186 @@ int sfm_sift(sfm_ctx* ctx, const uint8_t* gray, int32_t n_img, int32_t w, int32_
 int sfm_sift_host(const uint8_t* gray, int32_t n_img, int32_t w, int32_t h, const sfm_sift_options* opts,
                   int64_t cap_per_img, float* xyso, uint8_t* desc, int64_t* n_feat, sfm_sift_summary* summary);
 
+/* ------------------------------------------------------------------------ */
+/* Incremental reconstruction                                 */
+/* OpenMVG's SequentialSfMReconstructionEngine::Process() as reconstruction() */
+/* runs it (sparseBuilder.cpp:1283-1599: engine INCREMENTAL,                 */
+/* PINHOLE_CAMERA_RADIAL3, ADJUST_ALL), over the batch stages above.         */
+/* Restated from its published code, parity unpinned.         */
+/*                                                                          */
+/* Round queries.  The tracks do not change between rounds: a                */
+/* sfm_recon_tracks handle holds a sfm_ba_problem's structure (pt_offsets,   */
+/* obs_img, obs_uv) on the device (or, for the host twin, on the host) and   */
+/* answers three questions about the per-round state registered[n_img],      */
+/* pt_ok[n_pt] (uint8, != 0 is set) and X[3*n_pt].  An observation is alive  */
+/* until sfm_recon_tracks_drop_obs names it.  Every output is integral or a  */
+/* gather: a device handle and a host handle give the same bytes.            */
+/*   visibility  count[i] = the points p with pt_ok[p] that have at least    */
+/*               one alive observation in image i (two observations of one   */
+/*               point in one image count once), for every image.            */
+/*   gather      sfm_resect_gather over alive observations: for the images   */
+/*               listed, off[n_images+1] and X3 / uv, image by image, each   */
+/*               image's correspondences in the problem's observation order. */
+/*   select      the sub-problem of the alive observations whose image is    */
+/*               registered, over the points that qualify: SFM_RECON_NEW     */
+/*               pt_ok[p] == 0 and two such observations in different        */
+/*               images; SFM_RECON_SOLVED pt_ok[p] != 0 and at least         */
+/*               min_track_len (>= 1) such observations.  Points keep their  */
+/*               order and each point's observations theirs; pt_map[k] /     */
+/*               obs_map[k] = the old index of new point / observation k.    */
+/*                                                                          */
+/* The driver.  sfm_reconstruct(tracks, intr, wh, pairs):                    */
+/*   pair      every candidate pair (I, J) of pairs[]: its correspondences   */
+/*             are the tracks holding both images, in track order (an        */
+/*             image's first observation in the track); one sfm_relpose call */
+/*             over all pairs; the pair is the one the engine's rule picks   */
+/*             (status OK, n_front > pair_min_inliers, angle_median >        */
+/*             pair_min_angle_deg, the largest angle_median, the first on a  */
+/*             tie).  initial_pair[0] >= 0 names the pair instead: it only   */
+/*             has to come out SFM_RELPOSE_OK.  No pair: SFM_OK with         */
+/*             stats->status = SFM_RECON_NO_INITIAL_PAIR, nothing            */
+/*             registered.  Image I gets the identity, image J the result;   */
+/*             then `points` below.  No bundle adjustment runs on the pair   */
+/*             alone (OpenMVG adjusts it with the intrinsics held fixed;     */
+/*             this library has no fixed-intrinsics solve and two views with */
+/*             free intrinsics are ill-posed).                               */
+/*   round     visibility; best = the largest count over the images neither  */
+/*             registered nor tried; 0 ends the loop.  Candidates: those     */
+/*             images with count >= group_ratio * best, ascending; gather,   */
+/*             one sfm_resect call; every candidate is tried for good; those */
+/*             that come out SFM_RESECT_OK are registered at the refined     */
+/*             pose, and their correspondences outside the resection's       */
+/*             inliers are dropped for good (the engine adds the inliers to  */
+/*             its landmarks, nothing else).  Then `points`, then `adjust`.  */
+/*   points    select(NEW) -> sfm_triangulate(tri).  An OK point sets pt_ok  */
+/*             and X; its observations the triangulation did not keep are    */
+/*             dropped for good.                                             */
+/*   adjust    (adjust != 0) select(SOLVED, min_track_len) -> sfm_ba_solve   */
+/*             (const_img = image I of the pair, the tracks' huber_a) ->     */
+/*             sfm_ba_wash(wash).  A removed point gets pt_ok = 0, X = NaN   */
+/*             and may be triangulated again; a rejected observation of a    */
+/*             surviving point is dropped for good.  Repeats while the wash  */
+/*             took more than wash_repeat_above observations out of the      */
+/*             sub-problem, at most max_adjust_repeats times.  A solve that  */
+/*             is not usable leaves everything as it was and ends the step.  */
+/*             An observation whose image is registered after its point was  */
+/*             solved enters the next select(SOLVED); the wash judges it.    */
+/*   end       (adjust != 0) one more `adjust` with wash_repeat_above = 0.   */
+/* Round 0 of the log is the pair (two candidates: the images, count = the   */
+/* common tracks, status / n_inliers the relative pose's).  rounds[] and     */
+/* cands[] take what fits; stats->n_rounds / n_cands are the true counts.    */
+/* sfm_reconstruct_host runs the same driver over the host twins; the        */
+/* library has no host bundle adjustment, so adjust != 0 there is            */
+/* SFM_ERR_UNSUPPORTED.  With adjust == 0 both take the same decisions.      */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_recon_tracks sfm_recon_tracks;
+#define SFM_RECON_NEW    0
+#define SFM_RECON_SOLVED 1
+/* Argument checks (host, before any device call): a null pointer, negative
+ * counts, pt_offsets not running monotonically from 0 to n_obs, an image
+ * outside [0, n_img): SFM_ERR_INVALID_ARG; n_pt or n_obs >= 2^31 - 1:
+ * SFM_ERR_UNSUPPORTED.  img_intr, const_img, camera_model are not read. */
+int sfm_recon_tracks_create(sfm_ctx* ctx, const sfm_ba_problem* prob, sfm_recon_tracks** out);
+/* [cpu] the host twin of the handle */
+int sfm_recon_tracks_create_host(const sfm_ba_problem* prob, sfm_recon_tracks** out);
+int sfm_recon_tracks_destroy(sfm_recon_tracks* t);
+/* obs[n]: observations (old indices) that are no longer alive. */
+int sfm_recon_tracks_drop_obs(sfm_recon_tracks* t, const int64_t* obs, int64_t n);
+int sfm_recon_visibility(sfm_recon_tracks* t, const uint8_t* pt_ok, int32_t* count /* [n_img] */);
+/* off[n_images+1] is always the true layout; X3[3*cap] / uv[2*cap] are
+ * written only when off[n_images] <= cap (cap 0 with NULL arrays: the size
+ * query); obs[cap] (optional, with them): each row's old observation index.  An image out of range or listed twice: SFM_ERR_INVALID_ARG. */
+int sfm_recon_gather(sfm_recon_tracks* t, const double* X, const uint8_t* pt_ok, const int32_t* images,
+                     int32_t n_images, int64_t* off, double* X3, double* uv, int64_t* obs, int64_t cap);
+/* *n_pt_out / *n_obs_out are always the true sizes; pt_offsets[cap_pt+1],
+ * pt_map[cap_pt], obs_img / obs_map[cap_obs], obs_uv[2*cap_obs] are written
+ * only when both fit (caps 0 with NULL arrays: the size query). */
+int sfm_recon_select(sfm_recon_tracks* t, const uint8_t* registered, const uint8_t* pt_ok, int32_t mode,
+                     int32_t min_track_len, int64_t* n_pt_out, int64_t* n_obs_out, int64_t* pt_offsets,
+                     int32_t* obs_img, double* obs_uv, int64_t* pt_map, int64_t* obs_map, int64_t cap_pt,
+                     int64_t cap_obs);
+
+#define SFM_RECON_OK              0
+#define SFM_RECON_NO_INITIAL_PAIR 1
+typedef struct sfm_recon_opts {
+    sfm_relpose_opts relpose;     /* sfm_relpose_default_options                  */
+    sfm_resect_opts  resect;      /* sfm_resect_default_options                   */
+    sfm_tri_opts     tri;         /* sfm_tri_default_options                      */
+    sfm_ba_options   ba;          /* sfm_ba_default_options                       */
+    sfm_ba_wash_opts wash;        /* sfm_ba_wash_default_options                  */
+    int32_t initial_pair[2];      /* {-1, -1}: automatic                          */
+    int32_t pair_min_inliers;     /* 100                                          */
+    int32_t adjust;               /* 1                                            */
+    double  pair_min_angle_deg;   /* 3.0                                          */
+    double  group_ratio;          /* 0.75 (dThresholdGroup)                       */
+    int32_t wash_repeat_above;    /* 50                                           */
+    int32_t max_adjust_repeats;   /* 8 (>= 1)                                     */
+    int32_t min_track_len;        /* 2 (>= 1): select(SOLVED)                     */
+    int32_t reserved;
+} sfm_recon_opts;
+typedef struct sfm_recon_cand {
+    int32_t round, image;
+    int32_t count;                /* visibility count (round 0: common tracks)    */
+    int32_t status;               /* SFM_RESECT_* (round 0: SFM_RELPOSE_*)        */
+    int32_t n_inliers, reserved;
+} sfm_recon_cand;
+typedef struct sfm_recon_round {
+    int32_t first_cand, n_cand;   /* cands[first_cand .. first_cand + n_cand)     */
+    int32_t n_registered;         /* candidates registered in this round          */
+    int32_t adjust_repeats;       /* solves run (0: none)                          */
+    int64_t points_added;         /* triangulated OK                              */
+    int64_t obs_dropped;          /* by the triangulation and the washes          */
+    int64_t points_removed;       /* by the washes                                */
+    int32_t ba_rc, reserved;      /* the last solve's return code                 */
+    sfm_ba_summary ba;            /* the last solve                               */
+    sfm_ba_wash_stats wash;       /* the last wash                                */
+} sfm_recon_round;
+typedef struct sfm_recon_stats {
+    int32_t status;               /* SFM_RECON_*                                  */
+    int32_t initial_pair[2];      /* (I, J); -1 without                           */
+    int32_t n_rounds, n_cands;    /* true counts (the log may hold fewer)         */
+    int32_t n_registered;
+    int64_t n_points, n_obs_kept;
+    int64_t final_removed;        /* observations the last wash took out          */
+    sfm_recon_round final_adjust; /* the closing adjustment (adjust != 0)         */
+    double seconds[8];            /* wall: pair search, visibility, gather,
+                                     select, resect, triangulate, solve, wash    */
+} sfm_recon_stats;
+/* [cpu] the defaults above; NULL opts below select them. */
+void sfm_recon_default_options(sfm_recon_opts* opts);
+/* tracks: n_img, n_intr, n_pt, n_obs, pt_offsets, obs_img, obs_uv, img_intr,
+ * camera_model, huber_a (const_img is ignored).  intr[iw*n_intr] in / out
+ * (refined when adjust != 0), wh[2*n_img], pairs[2*n_pairs].  Outputs:
+ * extr[6*n_img] (0 for an unregistered image), X[3*n_pt] (NaN where the point
+ * is not reconstructed), registered[n_img], pt_ok[n_pt], keep_obs[n_obs] (the
+ * alive observations of reconstructed points in registered images); rounds /
+ * cands may be NULL with cap 0, stats may be NULL.  Every argument check runs
+ * on the host before any device call: the checks of sfm_recon_tracks_create,
+ * img_intr outside [0, n_intr), an unknown camera_model, a non-positive image
+ * size, a pair naming an image out of range or twice, negative capacities,
+ * group_ratio outside (0, 1], max_adjust_repeats or min_track_len < 1, and
+ * the stages' option checks: SFM_ERR_INVALID_ARG.  It does not shard. */
+int sfm_reconstruct(sfm_ctx* ctx, const sfm_ba_problem* tracks, double* intr, const int32_t* wh,
+                    const int32_t* pairs, int64_t n_pairs, const sfm_recon_opts* opts, double* extr, double* X,
+                    uint8_t* registered, uint8_t* pt_ok, uint8_t* keep_obs, sfm_recon_round* rounds,
+                    int32_t cap_rounds, sfm_recon_cand* cands, int32_t cap_cands, sfm_recon_stats* stats);
+/* [cpu] */
+int sfm_reconstruct_host(const sfm_ba_problem* tracks, double* intr, const int32_t* wh, const int32_t* pairs,
+                         int64_t n_pairs, const sfm_recon_opts* opts, double* extr, double* X,
+                         uint8_t* registered, uint8_t* pt_ok, uint8_t* keep_obs, sfm_recon_round* rounds,
+                         int32_t cap_rounds, sfm_recon_cand* cands, int32_t cap_cands, sfm_recon_stats* stats);
+
+/* sparseBuilder::reconstruction(), file-staged: sfm_data.json (views, sizes)
+ * + <stem>.feat + matches.f.bin -> sfm_sparse_tracks -> sfm_reconstruct with
+ * SFM_CAM_RADIAL3, one intrinsics block per view {focal, w/2, h/2, 0, 0, 0}
+ * (focal <= 0: 1.2 * max(w, h), OpenMVG's guess without EXIF), the candidate
+ * pairs those of the matches file -> <out_dir>/cloud_and_poses.ply in the
+ * layout of OpenMVG's plyHelper::exportToPly: ASCII, double x y z + uchar
+ * red green blue, the points in white, then the camera centres in green.
+ * sfm_data.bin (cereal binary) is not written.  opts NULL = the defaults. */
+int sfm_sparse_reconstruct(sfm_ctx* ctx, const char* matches_dir, const char* out_dir, double focal,
+                           const sfm_recon_opts* opts, sfm_recon_stats* stats);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
