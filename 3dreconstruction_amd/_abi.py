@@ -300,6 +300,11 @@ class ReconStats(C.Structure):
                 ("seconds", C.c_double * 8)]
 
 
+class ColorizeStats(C.Structure):
+    _fields_ = [("n_to_colour", C.c_int64), ("n_coloured", C.c_int64), ("n_rounds", C.c_int32),
+                ("reserved", C.c_int32), ("seconds", C.c_double * 3)]
+
+
 class SparseFilterStats(C.Structure):
     _fields_ = [("n_pairs_in", C.c_int64), ("n_pairs_out", C.c_int64), ("n_matches_in", C.c_int64),
                 ("n_matches_out", C.c_int64)]
@@ -395,6 +400,19 @@ SIGNATURES = [
                                        C.c_int32, C.POINTER(ReconCand), C.c_int32, C.POINTER(ReconStats)]),
     ("sfm_sparse_reconstruct", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_double, C.POINTER(ReconOpts),
                                          C.POINTER(ReconStats)]),
+    ("sfm_colorize_assign", C.c_int, [C.c_void_p, C.POINTER(BAProblem), i32p, u8p, u8p, i32p, i64p, i32p, i32p, i32p,
+                                      C.POINTER(ColorizeStats)]),
+    ("sfm_colorize_assign_host", C.c_int, [C.POINTER(BAProblem), i32p, u8p, u8p, i32p, i64p, i32p, i32p, i32p,
+                                           C.POINTER(ColorizeStats)]),
+    ("sfm_colorize_sample", C.c_int, [C.c_int64, i32p, i32p, C.c_int32, i32p, i32p, i64p, u8p, u8p]),
+    ("sfm_colorize", C.c_int, [C.c_void_p, C.POINTER(BAProblem), i32p, u8p, u8p, i32p, i64p, u8p, u8p, i32p,
+                               C.POINTER(ColorizeStats)]),
+    ("sfm_colorize_host", C.c_int, [C.POINTER(BAProblem), i32p, u8p, u8p, i32p, i64p, u8p, u8p, i32p,
+                                    C.POINTER(ColorizeStats)]),
+    ("sfm_colorize_write_ply", C.c_int, [C.c_char_p, C.c_int64, f64p, u8p, u8p, C.c_int32, f64p, u8p]),
+    ("sfm_sparse_reconstruct_colorize", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_double,
+                                                  C.POINTER(ReconOpts), i32p, i64p, u8p, C.POINTER(ReconStats),
+                                                  C.POINTER(ColorizeStats)]),
     ("sfm_sift_options_default", None, [C.POINTER(SiftOptions)]),
     ("sfm_sift", C.c_int, [C.c_void_p, u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
                            f32p, u8p, i64p, C.POINTER(SiftSummary)]),

@@ -1222,3 +1222,135 @@ def sparse_reconstruct(ctx, matches_dir, out_dir, focal=-1.0, opts=None):
                                              C.byref(opts) if opts is not None else None, C.byref(st)),
            "sfm_sparse_reconstruct")
     return _struct_dict(st)
+
+
+# ---- track colouring ------------------------------------------------------------------
+def _mask(a, n):
+    """an optional uint8 mask of n entries (None stays None: all)"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(a).astype(np.uint8).reshape(-1))
+    assert len(a) == n
+    return a if n else np.zeros(1, np.uint8)
+
+
+def colorize_assign(ctx, problem, wh, pt_ok=None, keep_obs=None):
+    """sfm_colorize_assign (ctx None: sfm_colorize_assign_host): which view
+    colours each point.  dict(view [n_pt], obs [n_pt], px [n_pt, 2],
+    order [n_img] (-1 from n_rounds on), n_rounds, stats)."""
+    lib = abi.load()
+    n_img, n_pt = problem.n_img, problem.n_pt
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    assert len(wh) == 2 * n_img
+    ok, keep = _mask(pt_ok, n_pt), _mask(keep_obs, problem.n_obs)
+    view = np.full(max(n_pt, 1), -7, np.int32)
+    obs = np.full(max(n_pt, 1), -7, np.int64)
+    px = np.full(2 * max(n_pt, 1), -7, np.int32)
+    order = np.full(max(n_img, 1), -7, np.int32)
+    n_rounds = C.c_int32(-7)
+    st = abi.ColorizeStats()
+    args = (C.byref(problem), abi.ptr(wh, abi.i32p), abi.ptr(ok, abi.u8p), abi.ptr(keep, abi.u8p),
+            abi.ptr(view, abi.i32p), abi.ptr(obs, abi.i64p), abi.ptr(px, abi.i32p), abi.ptr(order, abi.i32p),
+            C.byref(n_rounds), C.byref(st))
+    if ctx is None:
+        _check(lib.sfm_colorize_assign_host(*args), "sfm_colorize_assign_host")
+    else:
+        _check(lib.sfm_colorize_assign(ctx.h, *args), "sfm_colorize_assign")
+    return dict(view=view[:n_pt], obs=obs[:n_pt], px=px[:2 * n_pt].reshape(-1, 2), order=order[:n_img],
+                n_rounds=n_rounds.value, stats=_struct_dict(st))
+
+
+def colorize_assign_host(problem, wh, pt_ok=None, keep_obs=None):
+    return colorize_assign(None, problem, wh, pt_ok, keep_obs)
+
+
+def _pixel_pool(images):
+    """images: per view a uint8 array [h, w] / [h, w, 1] / [h, w, 3], or None
+    (not loaded) -> (channels, img_off, pixels) as sfm_colorize_sample reads them"""
+    channels = np.ones(max(len(images), 1), np.int32)
+    img_off = np.full(max(len(images), 1), -1, np.int64)
+    parts, at = [], 0
+    for i, im in enumerate(images):
+        if im is None:
+            continue
+        im = np.ascontiguousarray(im, np.uint8)
+        channels[i] = 1 if im.ndim == 2 else im.shape[2]
+        img_off[i] = at
+        parts.append(im.reshape(-1))
+        at += im.size
+    pixels = np.concatenate(parts) if parts else np.zeros(1, np.uint8)
+    return channels, img_off, pixels
+
+
+def colorize_sample(view, px, wh, images=None, pool=None):
+    """sfm_colorize_sample: rgb [n_pt, 3] from the images (a list, see
+    _pixel_pool) or a ready (channels, img_off, pixels) pool."""
+    view = np.ascontiguousarray(np.asarray(view, np.int32).reshape(-1))
+    px = np.ascontiguousarray(np.asarray(px, np.int32).reshape(-1))
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    n_pt, n_img = len(view), len(wh) // 2
+    assert len(px) == 2 * n_pt
+    channels, img_off, pixels = pool if pool is not None else _pixel_pool(images)
+    rgb = np.full(3 * max(n_pt, 1), 77, np.uint8)
+    _check(abi.load().sfm_colorize_sample(n_pt, abi.ptr(view if n_pt else np.zeros(1, np.int32), abi.i32p),
+                                          abi.ptr(px if n_pt else np.zeros(2, np.int32), abi.i32p), n_img,
+                                          abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p),
+                                          abi.ptr(channels, abi.i32p), abi.ptr(img_off, abi.i64p),
+                                          abi.ptr(pixels, abi.u8p), abi.ptr(rgb, abi.u8p)), "sfm_colorize_sample")
+    return rgb[:3 * n_pt].reshape(-1, 3)
+
+
+def colorize(ctx, problem, wh, images=None, pt_ok=None, keep_obs=None, pool=None):
+    """sfm_colorize (ctx None: sfm_colorize_host): assign and sample in one
+    call.  dict(rgb [n_pt, 3], view [n_pt], stats)."""
+    lib = abi.load()
+    n_img, n_pt = problem.n_img, problem.n_pt
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    assert len(wh) == 2 * n_img
+    ok, keep = _mask(pt_ok, n_pt), _mask(keep_obs, problem.n_obs)
+    channels, img_off, pixels = pool if pool is not None else _pixel_pool(images)
+    rgb = np.full(3 * max(n_pt, 1), 77, np.uint8)
+    view = np.full(max(n_pt, 1), -7, np.int32)
+    st = abi.ColorizeStats()
+    args = (C.byref(problem), abi.ptr(wh, abi.i32p), abi.ptr(ok, abi.u8p), abi.ptr(keep, abi.u8p),
+            abi.ptr(channels, abi.i32p), abi.ptr(img_off, abi.i64p), abi.ptr(pixels, abi.u8p), abi.ptr(rgb, abi.u8p),
+            abi.ptr(view, abi.i32p), C.byref(st))
+    if ctx is None:
+        _check(lib.sfm_colorize_host(*args), "sfm_colorize_host")
+    else:
+        _check(lib.sfm_colorize(ctx.h, *args), "sfm_colorize")
+    return dict(rgb=rgb[:3 * n_pt].reshape(-1, 3), view=view[:n_pt], stats=_struct_dict(st))
+
+
+def colorize_host(problem, wh, images=None, pt_ok=None, keep_obs=None, pool=None):
+    return colorize(None, problem, wh, images, pt_ok, keep_obs, pool)
+
+
+def colorize_write_ply(path, X, pt_ok=None, rgb=None, extr=None, registered=None):
+    """sfm_colorize_write_ply: the points with pt_ok (None: all) in their
+    colours (None: white), then the registered (None: all) camera centres."""
+    X = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1, 3))
+    extr = np.ascontiguousarray(np.zeros((0, 6)) if extr is None else np.asarray(extr, np.float64).reshape(-1, 6))
+    n_pt, n_img = len(X), len(extr)
+    if rgb is not None:
+        rgb = np.ascontiguousarray(np.asarray(rgb, np.uint8).reshape(-1))
+        assert len(rgb) == 3 * n_pt
+    _check(abi.load().sfm_colorize_write_ply(_b(path), n_pt, abi.ptr(X if n_pt else np.zeros(3), abi.f64p),
+                                             abi.ptr(_mask(pt_ok, n_pt), abi.u8p), abi.ptr(rgb, abi.u8p), n_img,
+                                             abi.ptr(extr if n_img else np.zeros(6), abi.f64p),
+                                             abi.ptr(_mask(registered, n_img), abi.u8p)), "sfm_colorize_write_ply")
+
+
+def sparse_reconstruct_colorize(ctx, matches_dir, out_dir, images, focal=-1.0, opts=None):
+    """sfm_sparse_reconstruct_colorize: reconstruction() + colorize(),
+    file-staged; images in the view order of sfm_data.json (see _pixel_pool).
+    Writes <out_dir>/cloud_and_poses.ply and <out_dir>/colorized.ply and
+    returns (reconstruction stats, colouring stats)."""
+    channels, img_off, pixels = _pixel_pool(images)
+    st, cs = abi.ReconStats(), abi.ColorizeStats()
+    _check(abi.load().sfm_sparse_reconstruct_colorize(ctx.h, _b(matches_dir), _b(out_dir), focal,
+                                                      C.byref(opts) if opts is not None else None,
+                                                      abi.ptr(channels, abi.i32p), abi.ptr(img_off, abi.i64p),
+                                                      abi.ptr(pixels, abi.u8p), C.byref(st), C.byref(cs)),
+           "sfm_sparse_reconstruct_colorize")
+    return _struct_dict(st), _struct_dict(cs)

@@ -3,7 +3,8 @@
 // serial host twins of the three round queries, and the driver
 // (sfm_reconstruct / sfm_reconstruct_host: one function over either kind of
 // handle and either set of stage entry points), plus the file-staged
-// sfm_sparse_reconstruct.  The round kernels are recon.hip's.
+// sfm_sparse_reconstruct and sfm_sparse_reconstruct_colorize.  The round
+// kernels are recon.hip's.
 //
 // Deviations from OpenMVG's SequentialSfMReconstructionEngine:
 // no bundle adjustment of the initial pair alone (no fixed-intrinsics solve
@@ -26,6 +27,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "colorize.h"
 #include "recon.h"
 #include "relpose_best.h"
 
@@ -56,66 +58,18 @@ void ok_or_throw(int rc) {
     if (rc != SFM_OK) throw SfmError{rc};
 }
 
-void check_tracks(const char* who, const sfm_ba_problem* P) {
-    SFM_REQUIRE(P, SFM_ERR_INVALID_ARG, "%s: null problem", who);
-    SFM_REQUIRE(P->n_img >= 0 && P->n_pt >= 0 && P->n_obs >= 0, SFM_ERR_INVALID_ARG, "%s: negative count", who);
-    SFM_REQUIRE(P->pt_offsets && (P->n_obs == 0 || (P->obs_img && P->obs_uv)), SFM_ERR_INVALID_ARG,
-                "%s: incomplete problem", who);
-    SFM_REQUIRE(P->pt_offsets[0] == 0 && P->pt_offsets[P->n_pt] == P->n_obs, SFM_ERR_INVALID_ARG,
-                "%s: pt_offsets must run from 0 to n_obs", who);
-    SFM_REQUIRE(P->n_obs < INT32_MAX && P->n_pt < INT32_MAX, SFM_ERR_UNSUPPORTED, "%s: 2^31 - 1 or more observations",
-                who);
-    for (int64_t p = 0; p < P->n_pt; ++p)
-        SFM_REQUIRE(P->pt_offsets[p + 1] >= P->pt_offsets[p], SFM_ERR_INVALID_ARG,
-                    "%s: pt_offsets not monotone at point %lld", who, (long long)p);
-    for (int64_t o = 0; o < P->n_obs; ++o)
-        SFM_REQUIRE(P->obs_img[o] >= 0 && P->obs_img[o] < P->n_img, SFM_ERR_INVALID_ARG,
-                    "%s: observation %lld names image %d", who, (long long)o, P->obs_img[o]);
-}
-
-// ---- the handle -------------------------------------------------------------------
-ReconIndex build_index(const sfm_ba_problem& P, std::vector<int32_t>& img_off) {
-    ReconIndex ix;
-    const size_t N = (size_t)P.n_obs;
-    ix.pt_off.resize((size_t)P.n_pt + 1);
-    ix.obs_pt.resize(N);
-    ix.dup.assign(N, 0);
-    img_off.assign((size_t)P.n_img + 1, 0);
-    std::vector<int64_t> first_at((size_t)P.n_img, -1);   // the point's first observation in the image ...
-    std::vector<int64_t> first_of((size_t)P.n_img, -1);   // ... valid while this names the point
-    for (int64_t p = 0; p <= P.n_pt; ++p) ix.pt_off[p] = (int32_t)P.pt_offsets[p];
-    for (int64_t p = 0; p < P.n_pt; ++p)
-        for (int64_t o = P.pt_offsets[p]; o < P.pt_offsets[p + 1]; ++o) {
-            const int32_t im = P.obs_img[o];
-            ix.obs_pt[o] = (int32_t)p;
-            ++img_off[(size_t)im + 1];
-            if (first_of[im] == p) {
-                ix.dup[o] = 1;
-                ix.dup[first_at[im]] = 1;
-            } else {
-                first_of[im] = p;
-                first_at[im] = o;
-            }
-        }
-    for (int32_t i = 0; i < P.n_img; ++i) img_off[(size_t)i + 1] += img_off[i];
-    ix.img_off = img_off;
-    ix.img_obs.resize(N);
-    std::vector<int32_t> at(img_off.begin(), img_off.end() - 1);
-    for (int64_t o = 0; o < P.n_obs; ++o) ix.img_obs[at[P.obs_img[o]]++] = (int32_t)o;
-    return ix;
-}
-
+// ---- the handle (its checks and its index: recon.h, shared with colorize.cpp) -------
 int create_handle(const char* who, sfm_ctx* ctx, bool device, const sfm_ba_problem* prob, sfm_recon_tracks** out) {
     return guarded([&] {
         SFM_REQUIRE(out, SFM_ERR_INVALID_ARG, "%s: null argument", who);
         *out = nullptr;
         SFM_REQUIRE(!device || ctx, SFM_ERR_INVALID_ARG, "%s: null context", who);
-        check_tracks(who, prob);
+        recon_check_tracks(who, prob);
         std::unique_ptr<sfm_recon_tracks> t(new sfm_recon_tracks);
         t->n_img = prob->n_img;
         t->n_pt = prob->n_pt;
         t->n_obs = prob->n_obs;
-        const ReconIndex ix = build_index(*prob, t->img_off);
+        const ReconIndex ix = recon_build_index(*prob, t->img_off);
         if (device) {
 #ifndef SFM_RECON_HOST_ONLY
             t->ctx = ctx;
@@ -411,7 +365,7 @@ int reconstruct(const char* who, sfm_ctx* ctx, bool device, const sfm_ba_problem
         sfm_recon_opts O;
         if (opts) O = *opts; else sfm_recon_default_options(&O);
         SFM_REQUIRE(!device || ctx, SFM_ERR_INVALID_ARG, "%s: null context", who);
-        check_tracks(who, prob);
+        recon_check_tracks(who, prob);
         const sfm_ba_problem& P = *prob;
         const int iw = sfm_ba_intr_width(P.camera_model);
         SFM_REQUIRE(iw > 0, SFM_ERR_INVALID_ARG, "%s: unknown camera_model %d", who, P.camera_model);
@@ -770,97 +724,128 @@ extern "C" int sfm_reconstruct(sfm_ctx* ctx, const sfm_ba_problem* tracks, doubl
                        pt_ok, keep_obs, rounds, cap_rounds, cands, cap_cands, stats);
 }
 
-// sparseBuilder::reconstruction(), file-staged
+// sparseBuilder::reconstruction(), file-staged: the scene in memory, shared by
+// sfm_sparse_reconstruct and sfm_sparse_reconstruct_colorize
+namespace {
+
+struct SparseScene {
+    int32_t n_img = 0;
+    std::vector<int64_t> pt_off;
+    std::vector<int32_t> obs_img, img_intr, wh;
+    std::vector<double> obs_uv, intr, extr, X;
+    std::vector<uint8_t> reg, pt_ok, keep;
+    sfm_ba_problem P;
+    sfm_recon_stats st;
+    std::string out_dir;   // with its trailing '/'
+};
+
+// before_device(n_img): the caller's remaining argument checks, run once the
+// number of views is known and before any device call
+template <class Check>
+void sparse_scene(const char* who, sfm_ctx* ctx, const char* matches_dir, const char* out_dir, double focal,
+                  const sfm_recon_opts* opts, const Check& before_device, SparseScene& sc) {
+    SFM_REQUIRE(ctx && matches_dir && out_dir, SFM_ERR_INVALID_ARG, "%s: null argument", who);
+    std::string dir(matches_dir);
+    sc.out_dir = out_dir;
+    if (!dir.empty() && dir.back() != '/') dir += '/';
+    if (!sc.out_dir.empty() && sc.out_dir.back() != '/') sc.out_dir += '/';
+    const std::string data = dir + "sfm_data.json";
+    int32_t n_img = 0;
+    ok_or_throw(sfm_mvg_load_views(data.c_str(), nullptr, 0, &n_img));
+    SFM_REQUIRE(n_img >= 2, SFM_ERR_INVALID_ARG, "%s: %d views", who, n_img);
+    before_device(n_img);
+    std::vector<sfm_mvg_view> views((size_t)n_img);
+    ok_or_throw(sfm_mvg_load_views(data.c_str(), views.data(), n_img, &n_img));
+    std::map<uint32_t, int32_t> slot;
+    for (int32_t k = 0; k < n_img; ++k) slot[views[k].id_view] = k;
+    // the candidate pairs: those of the matches file
+    const std::string mpath = dir + "matches.f.bin";
+    int64_t np = 0, nm = 0;
+    ok_or_throw(sfm_mvg_load_matches(mpath.c_str(), nullptr, nullptr, nullptr, nullptr, 0, 0, &np, &nm));
+    std::vector<int32_t> pairs(2 * (size_t)std::max<int64_t>(np, 1));
+    ok_or_throw(sfm_mvg_load_matches(mpath.c_str(), pairs.data(), nullptr, nullptr, nullptr, np, nm, &np, &nm));
+    for (int64_t k = 0; k < 2 * np; ++k) {
+        const auto it = slot.find((uint32_t)pairs[k]);
+        SFM_REQUIRE(it != slot.end(), SFM_ERR_INVALID_ARG, "%s: a match names view %d", who, pairs[k]);
+        pairs[k] = it->second;
+    }
+    // the tracks
+    struct TracksGuard {
+        sfm_tracks* t = nullptr;
+        ~TracksGuard() { sfm_tracks_destroy(t); }
+    } tg;
+    ok_or_throw(sfm_sparse_tracks(ctx, matches_dir, nullptr, nullptr, &tg.t));
+    sfm_tracks_stats ts;
+    ok_or_throw(sfm_tracks_get_stats(tg.t, &ts));
+    sc.pt_off.resize((size_t)ts.n_tracks + 1);
+    sc.obs_img.resize((size_t)std::max<int64_t>(ts.n_obs, 1));
+    sc.obs_uv.resize(2 * (size_t)std::max<int64_t>(ts.n_obs, 1));
+    ok_or_throw(sfm_tracks_fetch(tg.t, sc.pt_off.data(), sc.obs_img.data(), nullptr, sc.obs_uv.data()));
+    // PINHOLE_CAMERA_RADIAL3, one block per view, no distortion as the initial guess
+    sc.n_img = n_img;
+    sc.img_intr.resize((size_t)n_img);
+    sc.wh.resize(2 * (size_t)n_img);
+    sc.intr.assign(6 * (size_t)n_img, 0.0);
+    for (int32_t k = 0; k < n_img; ++k) {
+        const double w = views[k].width, h = views[k].height;
+        sc.img_intr[k] = k;
+        sc.wh[2 * k] = (int32_t)views[k].width;
+        sc.wh[2 * k + 1] = (int32_t)views[k].height;
+        sc.intr[6 * k] = focal > 0.0 ? focal : 1.2 * std::max(w, h);
+        sc.intr[6 * k + 1] = 0.5 * w;
+        sc.intr[6 * k + 2] = 0.5 * h;
+    }
+    sfm_ba_problem& P = sc.P;
+    std::memset(&P, 0, sizeof P);
+    P.n_img = n_img; P.n_intr = n_img; P.n_pt = ts.n_tracks; P.n_obs = ts.n_obs;
+    P.pt_offsets = sc.pt_off.data(); P.obs_img = sc.obs_img.data(); P.obs_uv = sc.obs_uv.data();
+    P.img_intr = sc.img_intr.data();
+    P.const_img = -1; P.camera_model = SFM_CAM_RADIAL3; P.huber_a = 4.0;
+    sc.extr.resize(6 * (size_t)n_img);
+    sc.X.resize(3 * (size_t)std::max<int64_t>(P.n_pt, 1));
+    sc.reg.resize((size_t)n_img);
+    sc.pt_ok.resize((size_t)std::max<int64_t>(P.n_pt, 1));
+    sc.keep.resize((size_t)std::max<int64_t>(P.n_obs, 1));
+    ok_or_throw(sfm_reconstruct(ctx, &P, sc.intr.data(), sc.wh.data(), pairs.data(), np, opts, sc.extr.data(),
+                                sc.X.data(), sc.reg.data(), sc.pt_ok.data(), sc.keep.data(), nullptr, 0, nullptr, 0,
+                                &sc.st));
+    // cloud_and_poses.ply: the points in white, then the camera centres C = -R' t in green
+    write_ply(who, (sc.out_dir + "cloud_and_poses.ply").c_str(), P.n_pt, sc.X.data(), sc.pt_ok.data(), nullptr, n_img,
+              sc.extr.data(), sc.reg.data());
+}
+
+}  // namespace
+
 extern "C" int sfm_sparse_reconstruct(sfm_ctx* ctx, const char* matches_dir, const char* out_dir, double focal,
                                       const sfm_recon_opts* opts, sfm_recon_stats* stats) {
     return guarded([&] {
-        SFM_REQUIRE(ctx && matches_dir && out_dir, SFM_ERR_INVALID_ARG, "sfm_sparse_reconstruct: null argument");
-        std::string dir(matches_dir), odir(out_dir);
-        if (!dir.empty() && dir.back() != '/') dir += '/';
-        if (!odir.empty() && odir.back() != '/') odir += '/';
-        const std::string data = dir + "sfm_data.json";
-        int32_t n_img = 0;
-        ok_or_throw(sfm_mvg_load_views(data.c_str(), nullptr, 0, &n_img));
-        SFM_REQUIRE(n_img >= 2, SFM_ERR_INVALID_ARG, "sfm_sparse_reconstruct: %d views", n_img);
-        std::vector<sfm_mvg_view> views((size_t)n_img);
-        ok_or_throw(sfm_mvg_load_views(data.c_str(), views.data(), n_img, &n_img));
-        std::map<uint32_t, int32_t> slot;
-        for (int32_t k = 0; k < n_img; ++k) slot[views[k].id_view] = k;
-        // the candidate pairs: those of the matches file
-        const std::string mpath = dir + "matches.f.bin";
-        int64_t np = 0, nm = 0;
-        ok_or_throw(sfm_mvg_load_matches(mpath.c_str(), nullptr, nullptr, nullptr, nullptr, 0, 0, &np, &nm));
-        std::vector<int32_t> pairs(2 * (size_t)std::max<int64_t>(np, 1));
-        ok_or_throw(sfm_mvg_load_matches(mpath.c_str(), pairs.data(), nullptr, nullptr, nullptr, np, nm, &np, &nm));
-        for (int64_t k = 0; k < 2 * np; ++k) {
-            const auto it = slot.find((uint32_t)pairs[k]);
-            SFM_REQUIRE(it != slot.end(), SFM_ERR_INVALID_ARG, "sfm_sparse_reconstruct: a match names view %d",
-                        pairs[k]);
-            pairs[k] = it->second;
-        }
-        // the tracks
-        struct TracksGuard {
-            sfm_tracks* t = nullptr;
-            ~TracksGuard() { sfm_tracks_destroy(t); }
-        } tg;
-        ok_or_throw(sfm_sparse_tracks(ctx, matches_dir, nullptr, nullptr, &tg.t));
-        sfm_tracks_stats ts;
-        ok_or_throw(sfm_tracks_get_stats(tg.t, &ts));
-        std::vector<int64_t> pt_off((size_t)ts.n_tracks + 1);
-        std::vector<int32_t> obs_img((size_t)std::max<int64_t>(ts.n_obs, 1));
-        std::vector<double> obs_uv(2 * (size_t)std::max<int64_t>(ts.n_obs, 1));
-        ok_or_throw(sfm_tracks_fetch(tg.t, pt_off.data(), obs_img.data(), nullptr, obs_uv.data()));
-        // PINHOLE_CAMERA_RADIAL3, one block per view, no distortion as the initial guess
-        std::vector<int32_t> img_intr((size_t)n_img), wh(2 * (size_t)n_img);
-        std::vector<double> intr(6 * (size_t)n_img, 0.0);
-        for (int32_t k = 0; k < n_img; ++k) {
-            const double w = views[k].width, h = views[k].height;
-            img_intr[k] = k;
-            wh[2 * k] = (int32_t)views[k].width;
-            wh[2 * k + 1] = (int32_t)views[k].height;
-            intr[6 * k] = focal > 0.0 ? focal : 1.2 * std::max(w, h);
-            intr[6 * k + 1] = 0.5 * w;
-            intr[6 * k + 2] = 0.5 * h;
-        }
-        sfm_ba_problem P;
-        std::memset(&P, 0, sizeof P);
-        P.n_img = n_img; P.n_intr = n_img; P.n_pt = ts.n_tracks; P.n_obs = ts.n_obs;
-        P.pt_offsets = pt_off.data(); P.obs_img = obs_img.data(); P.obs_uv = obs_uv.data(); P.img_intr = img_intr.data();
-        P.const_img = -1; P.camera_model = SFM_CAM_RADIAL3; P.huber_a = 4.0;
-        std::vector<double> extr(6 * (size_t)n_img), X(3 * (size_t)std::max<int64_t>(P.n_pt, 1));
-        std::vector<uint8_t> reg((size_t)n_img), pt_ok((size_t)std::max<int64_t>(P.n_pt, 1)),
-            keep((size_t)std::max<int64_t>(P.n_obs, 1));
-        sfm_recon_stats st;
-        ok_or_throw(sfm_reconstruct(ctx, &P, intr.data(), wh.data(), pairs.data(), np, opts, extr.data(), X.data(),
-                                    reg.data(), pt_ok.data(), keep.data(), nullptr, 0, nullptr, 0, &st));
-        if (stats) *stats = st;
-        // cloud_and_poses.ply: the points, then the camera centres C = -R' t in green
-        const std::string ply = odir + "cloud_and_poses.ply";
-        std::FILE* f = std::fopen(ply.c_str(), "w");
-        SFM_REQUIRE(f, SFM_ERR_INVALID_ARG, "sfm_sparse_reconstruct: cannot write %s", ply.c_str());
-        std::fprintf(f,
-                     "ply\nformat ascii 1.0\nelement vertex %lld\nproperty double x\nproperty double y\n"
-                     "property double z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
-                     (long long)(st.n_points + st.n_registered));
-        for (int64_t p = 0; p < P.n_pt; ++p)
-            if (pt_ok[p]) std::fprintf(f, "%.16f %.16f %.16f 255 255 255\n", X[3 * p], X[3 * p + 1], X[3 * p + 2]);
-        for (int32_t k = 0; k < n_img; ++k) {
-            if (!reg[k]) continue;
-            const double* e = &extr[6 * (size_t)k];
-            // C = -R' t, R' t by Rodrigues' formula with the angle negated
-            const double th2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2], th = std::sqrt(th2);
-            double C[3] = {e[3], e[4], e[5]};
-            if (th > 0.0) {
-                const double u[3] = {-e[0] / th, -e[1] / th, -e[2] / th}, c = std::cos(th), s = std::sin(th);
-                const double* t = e + 3;
-                const double d = u[0] * t[0] + u[1] * t[1] + u[2] * t[2];
-                const double x[3] = {u[1] * t[2] - u[2] * t[1], u[2] * t[0] - u[0] * t[2], u[0] * t[1] - u[1] * t[0]};
-                for (int a = 0; a < 3; ++a) C[a] = t[a] * c + x[a] * s + u[a] * d * (1 - c);
-            }
-            std::fprintf(f, "%.16f %.16f %.16f 0 255 0\n", -C[0], -C[1], -C[2]);
-        }
-        const bool good = std::fclose(f) == 0;
-        SFM_REQUIRE(good, SFM_ERR_INVALID_ARG, "sfm_sparse_reconstruct: writing %s failed", ply.c_str());
+        SparseScene sc;
+        sparse_scene("sfm_sparse_reconstruct", ctx, matches_dir, out_dir, focal, opts, [](int32_t) {}, sc);
+        if (stats) *stats = sc.st;
+        return SFM_OK;
+    });
+}
+
+// sparseBuilder::reconstruction() + colorize(), file-staged
+extern "C" int sfm_sparse_reconstruct_colorize(sfm_ctx* ctx, const char* matches_dir, const char* out_dir,
+                                               double focal, const sfm_recon_opts* opts, const int32_t* channels,
+                                               const int64_t* img_off, const uint8_t* pixels,
+                                               sfm_recon_stats* recon_stats, sfm_colorize_stats* color_stats) {
+    return guarded([&] {
+        const char* who = "sfm_sparse_reconstruct_colorize";
+        SparseScene sc;
+        sparse_scene(who, ctx, matches_dir, out_dir, focal, opts, [&](int32_t n_img) {
+            SFM_REQUIRE(channels && img_off, SFM_ERR_INVALID_ARG, "%s: null argument", who);
+            for (int32_t i = 0; i < n_img; ++i)
+                SFM_REQUIRE(img_off[i] < 0 || (pixels && (channels[i] == 1 || channels[i] == 3)), SFM_ERR_INVALID_ARG,
+                            "%s: image %d has %d channels, or no pixels", who, i, channels[i]);
+        }, sc);
+        if (recon_stats) *recon_stats = sc.st;
+        std::vector<uint8_t> rgb(3 * (size_t)std::max<int64_t>(sc.P.n_pt, 1));
+        ok_or_throw(sfm_colorize(ctx, &sc.P, sc.wh.data(), sc.pt_ok.data(), sc.keep.data(), channels, img_off, pixels,
+                                 rgb.data(), nullptr, color_stats));
+        write_ply(who, (sc.out_dir + "colorized.ply").c_str(), sc.P.n_pt, sc.X.data(), sc.pt_ok.data(), rgb.data(),
+                  sc.n_img, sc.extr.data(), sc.reg.data());
         return SFM_OK;
     });
 }

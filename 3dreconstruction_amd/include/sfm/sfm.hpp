@@ -14,6 +14,9 @@
 //   SequentialSfMReconstructionEngine  OpenMVG's incremental engine over the
 //                         stages above (reconstruction.hpp; sfm_reconstruct), and
 //                         sparseBuilder::reconstruction() file-staged
+//   ColorizeTracks        OpenMVG's greedy track colouring, what colorize() runs
+//                         (colorize.hpp; sfm_colorize), and sparseBuilder::colorize()
+//                         file-staged
 //   SIFT_Image_describer  src/nonFree/sift/SIFT_describer.hpp and detectFeature()
 //                         (sparseBuilder.cpp:575-756) on 8-bit gray buffers
 //                         (sift.hpp; sfm_sift)
@@ -43,6 +46,7 @@
 #include "../../../include/sfmcore.h"
 #include "actuator.hpp"
 #include "adjuster.hpp"
+#include "colorize.hpp"
 #include "frames.hpp"
 #include "localizer.hpp"
 #include "reconstruction.hpp"
@@ -222,6 +226,26 @@ class SequentialSfMReconstructionEngine : public BasicSequentialSfMReconstructio
 };
 
 // ---------------------------------------------------------------------------
+// ColorizeTracks (colorize.hpp) on the GPU: sfm_colorize
+// ---------------------------------------------------------------------------
+struct GpuColorizeBackend {
+    Context* ctx;
+    int colorize(const sfm_ba_problem& tracks, const int32_t* wh, const uint8_t* pt_ok, const uint8_t* keep_obs,
+                 const int32_t* channels, const int64_t* img_off, const uint8_t* pixels, uint8_t* rgb, int32_t* view,
+                 sfm_colorize_stats* stats) const {
+        return sfm_colorize(ctx->get(), &tracks, wh, pt_ok, keep_obs, channels, img_off, pixels, rgb, view, stats);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+inline bool ColorizeTracks(const WorldStructure& world, const std::vector<Image::Ptr>& images,
+                           const std::vector<ColorImage>& pixels, std::vector<std::array<uint8_t, 3>>& colors,
+                           Context& ctx = Context::thread_default(), const std::vector<uint8_t>* pt_ok = nullptr,
+                           sfm_colorize_stats* stats = nullptr) {
+    return ColorizeTracks(GpuColorizeBackend{&ctx}, world, images, pixels, colors, pt_ok, stats);
+}
+
+// ---------------------------------------------------------------------------
 // SIFT_Image_describer (sift.hpp) on the GPU: sfm_sift
 // ---------------------------------------------------------------------------
 struct GpuSiftBackend {
@@ -354,6 +378,29 @@ class sparseBuilder {
     }
     const sfm_recon_stats& reconstructionStats() const { return recon_stats_; }
 
+    // colorize() (:1601-1630) after reconstruction(): sfm_data.bin is not
+    // written, so no file carries the scene from one stage to the next, and
+    // this runs both (sfm_sparse_reconstruct_colorize): cloud_and_poses.ply as
+    // reconstruction() writes it, and colorized.ply beside it, by default
+    // <base>/output/reconstruction/colorized.ply.  images: the views' pixels in
+    // the view order of sfm_data.json (data == nullptr: not loaded).  The
+    // reference concatenates reconstruction_dir + "colorized.ply" without a
+    // separator (sparseBuilder.cpp:1604, main.cpp:281), which puts the file
+    // beside the directory under the name "reconstructioncolorized.ply"; that
+    // is not copied here.
+    void colorize(const std::vector<ColorImage>& images, double focal = -1.0, const std::string& out_dir = std::string()) {
+        const std::string out =
+            !out_dir.empty() ? out_dir
+            : matches_dir_.size() >= 7 ? matches_dir_.substr(0, matches_dir_.size() - 7) + "reconstruction"
+                                       : std::string(".");
+        const ColorPool pool(images);
+        last_rc_ = sfm_sparse_reconstruct_colorize(ctx_->get(), matches_dir_.c_str(), out.c_str(), focal, nullptr,
+                                                   pool.channels.data(), pool.img_off.data(), pool.pixels, &recon_stats_,
+                                                   &color_stats_);
+        if (last_rc_ != SFM_OK) std::fprintf(stderr, "colorize failed: %s\n", sfm_last_error());
+    }
+    const sfm_colorize_stats& colorizeStats() const { return color_stats_; }
+
     // in-memory regions: per view, n x 128 uint8 descriptors
     void setRegions(std::vector<std::vector<uint8_t>> regions) { regions_ = std::move(regions); }
     // exhaustivePairs(N) (:786)
@@ -404,6 +451,7 @@ class sparseBuilder {
     sfm_sparse_match_stats stats_{};
     sfm_sparse_filter_stats filter_stats_{};
     sfm_recon_stats recon_stats_{};
+    sfm_colorize_stats color_stats_{};
     std::vector<std::vector<uint8_t>> regions_;
 };
 

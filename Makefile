@@ -12,7 +12,7 @@ HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/
 
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
-     tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test
+     tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test tests/cpp/colorize_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -88,3 +88,9 @@ RECON_HOST_SRCS := $(CSRC)/recon.cpp $(CSRC)/relpose.cpp $(CSRC)/resect.cpp $(CS
 RECON_HOST_DEFS := -DSFM_RECON_HOST_ONLY -DSFM_RELPOSE_HOST_ONLY -DSFM_RESECT_HOST_ONLY -DSFM_TRI_HOST_ONLY
 tests/cpp/recon_test: tests/cpp/recon_test.cpp $(RECON_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -w $(RECON_HOST_DEFS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(RECON_HOST_SRCS)
+
+# sfm::ColorizeTracks on the host backend: csrc/colorize.cpp's host path (the
+# serial twin, the sampling, the PLY writer) compiled in (no library, no HIP
+# runtime: host only)
+tests/cpp/colorize_test: tests/cpp/colorize_test.cpp $(CSRC)/colorize.cpp $(HDRS)
+	g++ -O2 -std=c++17 -Wall -DSFM_COLORIZE_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(CSRC)/colorize.cpp

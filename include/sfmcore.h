@@ -1458,6 +1458,98 @@ int sfm_reconstruct_host(const sfm_ba_problem* tracks, double* intr, const int32
 int sfm_sparse_reconstruct(sfm_ctx* ctx, const char* matches_dir, const char* out_dir, double focal,
                            const sfm_recon_opts* opts, sfm_recon_stats* stats);
 
+/* ------------------------------------------------------------------------ */
+/* Track colouring                                           */
+/* sparseBuilder::colorize() (sparseBuilder.cpp:1601-1630): OpenMVG's        */
+/* ColorizeTracks, a greedy cover.  While uncoloured points remain: count    */
+/* for every view how many of them it sees, take the view that sees the      */
+/* most, give each of those points the pixel under its observation in that   */
+/* view.  Restated from its published description.                           */
+/*                                                                          */
+/* Inputs: the tracks as in sfm_ba_problem (n_img, n_pt, n_obs, pt_offsets,  */
+/* obs_img, obs_uv; nothing else is read), wh[2*n_img], pt_ok[n_pt] (the     */
+/* points to colour; NULL: all), keep_obs[n_obs] (the live observations;     */
+/* NULL: all): what sfm_reconstruct returns.  A point is to colour when      */
+/* pt_ok says so and it has a live observation.  A point counts once per     */
+/* image (OpenMVG's Observations is a map keyed by view): of several live    */
+/* observations of a track in one image the first in track order is used.    */
+/*   count[v]  the still uncoloured points to colour with a live             */
+/*             observation in v.                                             */
+/*   round     v = the view with the largest count; a tie goes to the lowest */
+/*             image index (OpenMVG sorts with std::sort, which leaves ties  */
+/*             unspecified; this library fixes them).  Every uncoloured      */
+/*             point seen in v gets view[p] = v, obs[p] = the observation    */
+/*             used, px[2p..] = ((int)clamp(u, 0, w-1), (int)clamp(v, 0,     */
+/*             h-1)), the clamp in double, then truncation, and leaves the   */
+/*             set.  The rounds stop when no count is positive.              */
+/* Outputs: view[n_pt] (-1 where the point is not coloured), obs[n_pt] (-1   */
+/* likewise), px[2*n_pt] (0 0 likewise), order[n_img] (the chosen views in   */
+/* order, -1 from n_rounds on), *n_rounds.  All integers: the device and the */
+/* host twin give the same bytes.                                            */
+/* The device chooses, the host samples: choosing is the whole cost (integer */
+/* work over the tracks), sampling is one pixel per point from images that   */
+/* are far too large to upload for that; and an image is needed only once a  */
+/* round has chosen it.  The device keeps count[] incrementally (a coloured  */
+/* point takes 1 off every image it is seen in) instead of recounting every  */
+/* round: O(n_obs + rounds * n_img) work.                                    */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_colorize_stats {
+    int64_t n_to_colour;          /* points with pt_ok and a live observation     */
+    int64_t n_coloured;           /* points with view >= 0                        */
+    int32_t n_rounds, reserved;
+    double seconds[3];            /* wall: index build (and upload), rounds,
+                                     download                                     */
+} sfm_colorize_stats;
+/* Every argument check runs on the host before any device call, and every
+ * violation is SFM_ERR_INVALID_ARG with a message: the checks of
+ * sfm_recon_tracks_create; n_pt or n_obs >= 2^31 - 1; a non-positive image
+ * size; a non-finite uv on a live observation of a point to colour.  stats may
+ * be NULL. */
+int sfm_colorize_assign(sfm_ctx* ctx, const sfm_ba_problem* tracks, const int32_t* wh, const uint8_t* pt_ok,
+                        const uint8_t* keep_obs, int32_t* view, int64_t* obs, int32_t* px, int32_t* order,
+                        int32_t* n_rounds, sfm_colorize_stats* stats);
+/* [cpu] the serial twin */
+int sfm_colorize_assign_host(const sfm_ba_problem* tracks, const int32_t* wh, const uint8_t* pt_ok,
+                             const uint8_t* keep_obs, int32_t* view, int64_t* obs, int32_t* px, int32_t* order,
+                             int32_t* n_rounds, sfm_colorize_stats* stats);
+/* [cpu] rgb[3p..] = the pixel of image view[p] at px[2p..]; 0 0 0 where
+ * view[p] < 0.  pixels is one byte pool: image i starts at byte img_off[i]
+ * (< 0: the caller did not load it), row-major, interleaved, row stride
+ * w * channels[i], channels[i] 1 (gives g g g) or 3 (read for loaded images
+ * only).  SFM_ERR_INVALID_ARG: a view outside [-1, n_img), a px outside its
+ * image, channels not 1 or 3, an unloaded image that some view[p] names. */
+int sfm_colorize_sample(int64_t n_pt, const int32_t* view, const int32_t* px, int32_t n_img, const int32_t* wh,
+                        const int32_t* channels, const int64_t* img_off, const uint8_t* pixels, uint8_t* rgb);
+/* Assign and sample in one call: rgb[3*n_pt]; view[n_pt] is optional (NULL).
+ * Beyond the checks above, before any device call: channels of a loaded image
+ * not 1 or 3, an unloaded image that has a live observation of a point to
+ * colour: SFM_ERR_INVALID_ARG. */
+int sfm_colorize(sfm_ctx* ctx, const sfm_ba_problem* tracks, const int32_t* wh, const uint8_t* pt_ok,
+                 const uint8_t* keep_obs, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                 uint8_t* rgb, int32_t* view, sfm_colorize_stats* stats);
+/* [cpu] */
+int sfm_colorize_host(const sfm_ba_problem* tracks, const int32_t* wh, const uint8_t* pt_ok,
+                      const uint8_t* keep_obs, const int32_t* channels, const int64_t* img_off,
+                      const uint8_t* pixels, uint8_t* rgb, int32_t* view, sfm_colorize_stats* stats);
+/* [cpu] colorized.ply, in the layout sfm_sparse_reconstruct writes: ASCII,
+ * double x y z ("%.16f") + uchar red green blue, the points with pt_ok (NULL:
+ * all) ascending, each in its colour rgb[3p..] (rgb NULL: white), then the
+ * centres C = -R' t of the registered (NULL: all) cameras in green. */
+int sfm_colorize_write_ply(const char* path, int64_t n_pt, const double* X, const uint8_t* pt_ok,
+                           const uint8_t* rgb, int32_t n_img, const double* extr, const uint8_t* registered);
+/* sparseBuilder::reconstruction() + colorize(), file-staged:
+ * sfm_sparse_reconstruct, then sfm_colorize over the pt_ok / keep_obs it
+ * returned, with the views of sfm_data.json as the images (channels, img_off,
+ * pixels as above, in the file's view order).  Writes
+ * <out_dir>/cloud_and_poses.ply (the same bytes as sfm_sparse_reconstruct) and
+ * <out_dir>/colorized.ply.  One call, because sfm_data.bin is not written: no
+ * file carries the scene from one stage to the next.  Either stats may be
+ * NULL. */
+int sfm_sparse_reconstruct_colorize(sfm_ctx* ctx, const char* matches_dir, const char* out_dir, double focal,
+                                    const sfm_recon_opts* opts, const int32_t* channels, const int64_t* img_off,
+                                    const uint8_t* pixels, sfm_recon_stats* recon_stats,
+                                    sfm_colorize_stats* color_stats);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
