@@ -1,5 +1,7 @@
 // BA point elimination (ba_schur): chunk points into MFMA tiles
 // (schur_kernel), general points into Z rows (zbatch_kernel, zpoint_kernel).
+#include <type_traits>
+
 #include "ba_device.h"
 namespace sfm {
 namespace {
@@ -29,12 +31,19 @@ struct alignas(16) CamPreL {
 };
 // next wave batch from p0: <= kSubPts points and <= kSubObs observations
 // (cpoff = chunk-relative point offsets in LDS); returns its point count
-template <int SP = kSubPts, int SO = kSubObs>
-__device__ __forceinline__ int batch_points(const int* cpoff, int p0, int np) {
-    const int lane = threadIdx.x & 63, q1 = p0 + 1 + lane;
-    const bool fits = lane < SP && q1 <= np && cpoff[q1] - cpoff[p0] <= SO;
-    return __builtin_ctzll(~__ballot(fits));
+// (batch_fits, ba_types.h, is the rule: the first lane that does not fit ends the batch)
+template <int SP = kSubPts, int SO = kSubObs, class Off>
+__device__ __forceinline__ int batch_points(const Off* cpoff, int p0, int np) {
+    const int lane = threadIdx.x & 63;
+    return __builtin_ctzll(~__ballot(batch_fits(cpoff, p0, lane, np, SP, SO)));
 }
+
+// rows of an LDS array at a compile-time stride S (in doubles)
+template <int S>
+struct LdsRows {
+    double* p;
+    __device__ __forceinline__ double* operator[](int q) const { return p + q * S; }
+};
 
 // lower 16x16 tiles (ti >= tj) of the NT x NT tile grid, row-major
 __device__ constexpr int kTi[15] = {0, 1, 1, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 4};
@@ -44,6 +53,21 @@ __device__ constexpr int kTj[15] = {0, 0, 1, 0, 1, 2, 0, 1, 2, 3, 0, 1, 2, 3, 4}
 // NT = 4: rows 0..63 F blocks; -Z w (64 values) is a VALU dot product per lane.
 // SP / SO: points / observations per wave batch.  The panel holds 3 columns
 // per point padded to the MFMA k of 4 and NT*16 rows (NT = 4 keeps w apart).
+// The pinhole NT = 4 kernel (kSlim) keeps its per-wave LDS small (8 one-wave
+// workgroups per CU need <= 20480 B each, staging included), which is what
+// lets it batch 6 points: only the 3 SP used panel columns are
+// stored (the padding of the last k-step is read as literal zeros), the
+// per-observation V | g_E shares lie over the panel (dead before phase B
+// fills it, so the panel is zeroed after the per-point sums), J_intr and M
+// share one odd-stride row per observation, and the chunk offsets and
+// intrinsics rows are 16- and 8-bit.  With 6 points, phase C's 12 sums per
+// point pass 64 lanes: with one intrinsics block in the chunk a lane takes
+// the two columns that share an M entry (36 lanes); a chunk with several
+// blocks takes the lane-per-(point, axis) sums (18 lanes x 4 sums, where 5
+// points ran 60 lanes x 1: 9 % slower per launch than 5 / 52 on two-block
+// chunks).  The BAL
+// and RADIAL3 NT = 4 kernels and every NT = 5 kernel keep the wide layout
+// and their code.
 // SE: the solve's first pass also forms the Jacobi point scales (what
 // point_scale_kernel computes) from the unscaled Jx it linearises anyway,
 // writes them to scaleE and uses them, instead of a separate pass.
@@ -77,7 +101,11 @@ __global__ __launch_bounds__(64 * schur_group(NT)) __attribute__((amdgpu_waves_p
     constexpr int kComb = 5;                    // tiles per round of the group's tile sum
     // each wave's own LDS; its space also carries the wave's tiles to wave 0
     // at the end (kComb 16x16 tiles per round)
-    struct WaveLds {
+    constexpr bool kSlim = NT == 4 && CM == SFM_CAM_PINHOLE;
+    constexpr int kPKs = kSlim ? 3 * SP : kPK;  // panel columns stored
+    constexpr int kObU = CM == SFM_CAM_PINHOLE ? 4 : 2 * NK;   // J_intr values per observation
+    constexpr int kRow = (kObU + 6) | 1;        // slim: J_intr | M row, odd stride
+    struct WaveLdsWide {
         double panel[kPK][kPS];                 // [k][row]
         double wcol[NT == 4 ? kPK : 1];         // NT = 4: w = L^-1 g_E per panel column
         double ob[SO][kOb];                     // J_intr nonzeros (scaled) | pad
@@ -88,6 +116,20 @@ __global__ __launch_bounds__(64 * schur_group(NT)) __attribute__((amdgpu_waves_p
         int orow[SO];                           // tile row of the obs' intrinsics block
         int cpoff[kChunkPts + 1];               // chunk point offsets, relative to obs_begin
     };
+    struct WaveLdsSlim {
+        union {
+            double panel[kPKs][kPS];            // [k][row], from phase B on
+            double vs[SO][9];                   // Jx'Jx (6) | Jx'f (3) until the per-point sums
+        };
+        double wcol[kPKs];                      // w = L^-1 g_E per panel column
+        double row[SO][kRow];                   // J_intr nonzeros (scaled) | M = Jx L^-T (6) | pad
+        double vsum[SP][10];                    // per point: V (6) | g_E (3)
+        unsigned short cpoff[kChunkPts + 1];    // chunk point offsets, relative to obs_begin
+        unsigned char orow[SO];                 // tile row of the obs' intrinsics block
+    };
+    static_assert(!kSlim || (sizeof(double) * SO * 9 <= sizeof(double) * kPKs * kPS && kChunkPts * SO < 65536),
+                  "slim layout: the shares fit the panel, the offsets 16 bits");
+    using WaveLds = std::conditional_t<kSlim, WaveLdsSlim, WaveLdsWide>;
     union WaveU {
         WaveLds w;
         double comb[kComb * 256 + 64];          // kComb tiles + the NT = 4 -Zw column
@@ -106,14 +148,21 @@ __global__ __launch_bounds__(64 * schur_group(NT)) __attribute__((amdgpu_waves_p
     const int c = c0 + (wave < n_sub ? wave : 0);   // this wave's chunk (a wave past the group's chunks idles)
     const ChunkDesc& cd = P.chunks[c];
     WaveLds& W = wl[wave].w;
-    double (&panel)[kPK][kPS] = W.panel;
-    double (&wcol)[NT == 4 ? kPK : 1] = W.wcol;
-    double (&ob)[SO][kOb] = W.ob;
-    double (&vs)[SO][9] = W.vs;
+    double (&panel)[kPKs][kPS] = W.panel;
+    auto& wcol = W.wcol;
+    const LdsRows<9> vs{&W.vs[0][0]};
+    LdsRows<kSlim ? kRow : kOb> ob;
+    LdsRows<kSlim ? kRow : 9> obm;
+    if constexpr (kSlim) {
+        ob.p = &W.row[0][0];
+        obm.p = &W.row[0][kObU];
+    } else {
+        ob.p = &W.ob[0][0];
+        obm.p = &W.vs[0][0];
+    }
     double (&vsum)[SP][10] = W.vsum;
-    double (*const obm)[9] = vs;
-    int (&orow)[SO] = W.orow;
-    int (&cpoff)[kChunkPts + 1] = W.cpoff;
+    auto& orow = W.orow;
+    auto& cpoff = W.cpoff;
     const int pb = cd.pt_begin, np = wave < n_sub ? cd.pt_end - pb : 0, ob0 = cd.obs_begin;
     // read once: a ChunkDesc load inside the batch loop would be waited on
     // with the in-order counter, i.e. together with the next batch's prefetch
@@ -191,11 +240,14 @@ __global__ __launch_bounds__(64 * schur_group(NT)) __attribute__((amdgpu_waves_p
         const double Xp[3] = {nx.Xp[0], nx.Xp[1], nx.Xp[2]};
         double sE[3] = {nx.sE[0], nx.sE[1], nx.sE[2]};
         fetch(p1, nx);
+        auto zero_panel = [&]() {
 #pragma unroll
-        for (int e = lane; e < kPK * kPS / 2; e += 64)
-            reinterpret_cast<double2*>(&panel[0][0])[e] = double2{0.0, 0.0};
-        if constexpr (NT == 4)
-            if (lane < kPK) wcol[lane] = 0.0;   // columns past 3 * npts stay zero
+            for (int e = lane; e < kPKs * kPS / 2; e += 64)
+                reinterpret_cast<double2*>(&panel[0][0])[e] = double2{0.0, 0.0};
+            if constexpr (NT == 4)
+                if (lane < kPKs) wcol[lane] = 0.0;   // columns past 3 * npts stay zero
+        };
+        if constexpr (!kSlim) zero_panel();
         SFM_STAMP(0)
         // ---- A: observations -> scaled, corrected Jacobians -----------------
         LinT<CM> L;
@@ -281,6 +333,10 @@ __global__ __launch_bounds__(64 * schur_group(NT)) __attribute__((amdgpu_waves_p
             vsum[pt][e] = acc;
         }
         wsync();
+        if constexpr (kSlim) {   // the shares are summed: their space becomes the panel
+            zero_panel();
+            wsync();
+        }
         SFM_STAMP(1)
         // ---- B: every observation lane takes its point's V + D^2 and g_E (the
         // per-point sums above: identical on all lanes of the point), factors
@@ -340,7 +396,29 @@ __global__ __launch_bounds__(64 * schur_group(NT)) __attribute__((amdgpu_waves_p
         // SequentialActuator's single camera): every observation has the same
         // row, so the sums run without the run-boundary test (same fma order,
         // same bits as the general loops below).
-        if (one_intr) {
+        if (kSlim && one_intr && 12 * SP > 64) {
+            // 12 sums per point pass 64 lanes: one lane per (point, axis, M
+            // row r) takes columns r and r + 2, which share M[r][a] (each
+            // sum's fma order as below)
+            const int row = irow[0];
+            if (lane < 6 * npts) {
+                const int pt = lane / 6, rem = lane - 6 * pt, a = rem >> 1, r = rem & 1;
+                const int mo = 3 * r + a;
+                const int q0 = cpoff[p0 + pt] - o0, q1 = cpoff[p0 + pt + 1] - o0;
+                double z0 = 0.0, z2 = 0.0;
+                int q = q0;
+                for (; q + 4 <= q1; q += 4) {
+                    double j0[4], j2[4], mv[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { j0[j] = ob[q + j][r]; j2[j] = ob[q + j][r + 2]; mv[j] = obm[q + j][mo]; }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { z0 = fma(j0[j], mv[j], z0); z2 = fma(j2[j], mv[j], z2); }
+                }
+                for (; q < q1; ++q) { z0 = fma(ob[q][r], obm[q][mo], z0); z2 = fma(ob[q][r + 2], obm[q][mo], z2); }
+                panel[3 * pt + a][row + r] += z0;
+                panel[3 * pt + a][row + r + 2] += z2;
+            }
+        } else if (one_intr) {
             constexpr int NZ = 3 * NK;   // (axis, column) sums per point
             const int row = irow[0];
             for (int e = lane; e < NZ * npts; e += 64) {
@@ -450,14 +528,16 @@ __global__ __launch_bounds__(64 * schur_group(NT)) __attribute__((amdgpu_waves_p
         wsync();
         SFM_STAMP(3)
         // ---- D: tile += panel panel' on the fp64 MFMA -------------------------
-        // all operands first (padding columns are zero), then the MFMAs
+        // all operands first (padding columns are zero: stored, or literal
+        // where the panel ends at 3 SP columns), then the MFMAs
         const int kk = lane >> 4, ii = lane & 15;
         constexpr int kKs = kPK / 4;
         double op[kKs][NT];
 #pragma unroll
         for (int ks = 0; ks < kKs; ++ks)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) op[ks][t] = panel[4 * ks + kk][16 * t + ii];
+            for (int t = 0; t < NT; ++t)
+                op[ks][t] = (4 * ks + 3 < kPKs || 4 * ks + kk < kPKs) ? panel[4 * ks + kk][16 * t + ii] : 0.0;
 #pragma unroll
         for (int ks = 0; ks < kKs; ++ks)
 #pragma unroll
@@ -465,7 +545,7 @@ __global__ __launch_bounds__(64 * schur_group(NT)) __attribute__((amdgpu_waves_p
                 acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(op[ks][kTi[q]], op[ks][kTj[q]], acc[q], 0, 0, 0);
         if constexpr (NT == 4) {
 #pragma unroll
-            for (int k = 0; k < kPK; ++k) wacc += panel[k][lane] * wcol[k];
+            for (int k = 0; k < kPKs; ++k) wacc += panel[k][lane] * wcol[k];
         }
         wsync();
         SFM_STAMP(4)
@@ -894,7 +974,11 @@ void ba_schur(const DevProblem& P, const CamPre* cp, const double* intr, const d
         }
         if (P.n_group <= 0) return;
         // 64-row tiles: batches of schur4_pts(CM) points (ba_types.h) at 8 waves
-        // per CU (6-point batches' LDS allows 7, and measured 9% slower)
+        // per CU.  Pinhole runs 6 points / 60 observations: with the wide
+        // per-wave layout that shape's LDS allowed fewer waves and measured 9%
+        // slower than 5 / 52; with the slim layout it is 20384 B per one-wave
+        // workgroup (8 fit 160 KB) and C4 measured 358.7 -> 339.9 us per
+        // launch, 1159 -> 1192 LM-iters/s (profiles/r07/a_batch6)
         const dim3 grid(P.n_group), block(64 * schur_group(P.tile_nt));
         if (P.tile_nt == 4)
             SFM_BY_MODEL_ALL(P, hipLaunchKernelGGL((schur_kernel<CM, 4, schur4_pts(CM), schur4_obs(CM), SE>), grid, block,

@@ -27,13 +27,31 @@ constexpr int kZShortObs = 32;            // general points the batched Z kernel
 constexpr int kZBatchPts = 16;            // points per batch of that kernel
 constexpr int kSubObs = 64;               // observations per wave batch (one per lane)
 // points / observations per batch of the 64-row Schur variant, by residual
-// model (SFM_CAM_*: 0 pinhole, 1 BAL, 2 RADIAL3), sized so its LDS stays
-// under 20 KB, i.e. 8 waves per CU (the register limit): pinhole 5 / 52
-// (20.2 KB), BAL 4 / 48 (17.8 KB; 5 points would pass 20 KB), RADIAL3 4 / 44
-// (19.4 KB; 48 observations: 20.1 KB, 7 waves).  A point above the
-// observation count goes to the 80-row variant.
-constexpr int schur4_pts(int cm) { return cm == 0 ? 5 : 4; }
-constexpr int schur4_obs(int cm) { return cm == 0 ? 52 : cm == 2 ? 44 : 48; }
+// model (SFM_CAM_*: 0 pinhole, 1 BAL, 2 RADIAL3), sized so a one-wave
+// workgroup's LDS (the wave's own plus its staged cameras) stays within
+// 20480 B, i.e. 8 waves per CU of 160 KB (the register limit): pinhole
+// 6 / 60 (20384 B with the slim per-wave layout of ba_schur.hip; the wide
+// layout's 6 / 64 took 23.8 KB: fewer waves, 9 % slower), BAL 4 / 48
+// (18176 B) and RADIAL3 4 / 44 (19888 B) with the wide layout.  A point
+// above the observation count goes to the 80-row variant.
+constexpr int schur4_pts(int cm) { return cm == 0 ? 6 : 4; }
+constexpr int schur4_obs(int cm) { return cm == 0 ? 60 : cm == 2 ? 44 : 48; }
+// The Schur kernel's batch rule: with off[] the chunk's point offsets (np + 1
+// entries), point p0 + j joins the batch that starts at p0 if j < sp, the
+// point exists and the batch through it holds at most so observations.  A
+// batch is the longest run j = 0, 1, ... that fits (batch_count; the kernel
+// takes it by ballot).  It is empty only for a point above so observations,
+// which the planner keeps off that kernel.
+template <class Off>
+constexpr bool batch_fits(const Off* off, int p0, int j, int np, int sp, int so) {
+    return j < sp && p0 + 1 + j <= np && (int)off[p0 + 1 + j] - (int)off[p0] <= so;
+}
+template <class Off>
+constexpr int batch_count(const Off* off, int p0, int np, int sp, int so) {
+    int j = 0;
+    while (batch_fits(off, p0, j, np, sp, so)) ++j;
+    return j;
+}
 constexpr int kChunkPts = 128;            // points per chunk (upper bound; step_kernel threads)
 constexpr int kGroupChunks = 4;           // chunks per tile group, at most (the Schur kernel's waves per workgroup)
 // chunks per tile group by tile height: 4 for 64-row tiles (four waves' LDS

@@ -12,7 +12,8 @@ HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/
 
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
-     tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test tests/cpp/colorize_test
+     tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test tests/cpp/colorize_test \
+     tests/cpp/batch_points_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -94,3 +95,7 @@ tests/cpp/recon_test: tests/cpp/recon_test.cpp $(RECON_HOST_SRCS) $(HDRS)
 # runtime: host only)
 tests/cpp/colorize_test: tests/cpp/colorize_test.cpp $(CSRC)/colorize.cpp $(HDRS)
 	g++ -O2 -std=c++17 -Wall -DSFM_COLORIZE_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(CSRC)/colorize.cpp
+
+# the Schur kernel's batch rule (csrc/ba_types.h batch_fits / batch_count) walked on the host
+tests/cpp/batch_points_test: tests/cpp/batch_points_test.cpp $(CSRC)/ba_types.h
+	g++ -O2 -std=c++17 -Wall -o $@ $<
