@@ -305,6 +305,21 @@ class ColorizeStats(C.Structure):
                 ("reserved", C.c_int32), ("seconds", C.c_double * 3)]
 
 
+class UndistortOpts(C.Structure):
+    _fields_ = [("chunk_bytes", C.c_int64), ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8 * 5)]
+
+
+class UndistortStats(C.Structure):
+    _fields_ = [("n_images", C.c_int64), ("n_copied", C.c_int64), ("n_pixels", C.c_int64), ("n_outside", C.c_int64),
+                ("n_low_weight", C.c_int64), ("n_chunks", C.c_int32), ("reserved", C.c_int32),
+                ("seconds", C.c_double * 3)]
+
+
+class DenseSceneInfo(C.Structure):
+    _fields_ = [("n_platforms", C.c_int32), ("n_images", C.c_int32), ("n_vertices", C.c_int64),
+                ("n_views", C.c_int64), ("n_short", C.c_int64)]
+
+
 class SparseFilterStats(C.Structure):
     _fields_ = [("n_pairs_in", C.c_int64), ("n_pairs_out", C.c_int64), ("n_matches_in", C.c_int64),
                 ("n_matches_out", C.c_int64)]
@@ -413,6 +428,18 @@ SIGNATURES = [
     ("sfm_sparse_reconstruct_colorize", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_double,
                                                   C.POINTER(ReconOpts), i32p, i64p, u8p, C.POINTER(ReconStats),
                                                   C.POINTER(ColorizeStats)]),
+    ("sfm_undistort_default_options", None, [C.POINTER(UndistortOpts)]),
+    ("sfm_undistort", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, i32p, i32p, i64p, u8p,
+                                C.POINTER(UndistortOpts), u8p, C.POINTER(UndistortStats)]),
+    ("sfm_undistort_host", C.c_int, [C.c_int32, C.c_int32, C.c_int32, i32p, f64p, i32p, i32p, i64p, u8p,
+                                     C.POINTER(UndistortOpts), u8p, C.POINTER(UndistortStats)]),
+    ("sfm_undistort_write_pnm", C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, u8p]),
+    ("sfm_dense_scene_build", C.c_int, [C.POINTER(BAProblem), f64p, f64p, f64p, i32p, u8p, u8p, u8p,
+                                        C.POINTER(C.c_void_p)]),
+    ("sfm_dense_scene_get_info", C.c_int, [C.c_void_p, C.POINTER(DenseSceneInfo)]),
+    ("sfm_dense_scene_fetch", C.c_int, [C.c_void_p, f64p, i32p, i32p, i32p, i32p, f64p, f64p, f32p, i64p, u32p,
+                                        i64p]),
+    ("sfm_dense_scene_destroy", C.c_int, [C.c_void_p]),
     ("sfm_sift_options_default", None, [C.POINTER(SiftOptions)]),
     ("sfm_sift", C.c_int, [C.c_void_p, u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
                            f32p, u8p, i64p, C.POINTER(SiftSummary)]),

@@ -1354,3 +1354,100 @@ def sparse_reconstruct_colorize(ctx, matches_dir, out_dir, images, focal=-1.0, o
                                                       abi.ptr(pixels, abi.u8p), C.byref(st), C.byref(cs)),
            "sfm_sparse_reconstruct_colorize")
     return _struct_dict(st), _struct_dict(cs)
+
+
+# ---- dense hand-off -------------------------------------------------------------------
+def undistort_default_options():
+    o = abi.UndistortOpts()
+    abi.load().sfm_undistort_default_options(C.byref(o))
+    return o
+
+
+def undistort(ctx, camera_model, img_intr, intr, wh, images=None, opts=None, pool=None, out=None):
+    """sfm_undistort (ctx None: sfm_undistort_host): every loaded image
+    undistorted.  images: a list as in _pixel_pool, or a ready (channels,
+    img_off, pixels) pool.  out: the byte pool to write into (as large as
+    pixels; by default a zeroed one).  dict(out (the pool), images (views of
+    it, one per image, None where not loaded), stats)."""
+    lib = abi.load()
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    n_img = len(wh) // 2
+    img_intr = np.ascontiguousarray(np.asarray(img_intr, np.int32).reshape(-1))
+    assert len(img_intr) == n_img
+    iw = max(lib.sfm_ba_intr_width(camera_model), 1)
+    intr = np.ascontiguousarray(np.asarray(intr, np.float64).reshape(-1))
+    assert len(intr) % iw == 0
+    n_intr = len(intr) // iw
+    channels, img_off, pixels = pool if pool is not None else _pixel_pool(images)
+    if out is None:
+        out = np.zeros(len(pixels), np.uint8)
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and len(out) >= len(pixels)
+    st = abi.UndistortStats()
+    args = (camera_model, n_img, n_intr, abi.ptr(img_intr if n_img else np.zeros(1, np.int32), abi.i32p),
+            abi.ptr(intr if n_intr else np.zeros(1), abi.f64p), abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p),
+            abi.ptr(channels, abi.i32p), abi.ptr(img_off, abi.i64p), abi.ptr(pixels, abi.u8p),
+            C.byref(opts) if opts is not None else None, abi.ptr(out, abi.u8p), C.byref(st))
+    if ctx is None:
+        _check(lib.sfm_undistort_host(*args), "sfm_undistort_host")
+    else:
+        _check(lib.sfm_undistort(ctx.h, *args), "sfm_undistort")
+    views = []
+    for i in range(n_img):
+        if img_off[i] < 0:
+            views.append(None)
+            continue
+        w, h, ch = int(wh[2 * i]), int(wh[2 * i + 1]), int(channels[i])
+        v = out[img_off[i]:img_off[i] + w * h * ch]
+        views.append(v.reshape(h, w) if ch == 1 else v.reshape(h, w, ch))
+    return dict(out=out, images=views, stats=_struct_dict(st))
+
+
+def undistort_host(camera_model, img_intr, intr, wh, images=None, opts=None, pool=None, out=None):
+    return undistort(None, camera_model, img_intr, intr, wh, images, opts, pool, out)
+
+
+def write_pnm(path, image):
+    """sfm_undistort_write_pnm: a uint8 [h, w] / [h, w, 1] image as binary P5, [h, w, 3] as P6."""
+    im = np.ascontiguousarray(image, np.uint8)
+    ch = 1 if im.ndim == 2 else im.shape[2]
+    _check(abi.load().sfm_undistort_write_pnm(_b(path), im.shape[1], im.shape[0], ch, abi.ptr(im.reshape(-1), abi.u8p)),
+           "sfm_undistort_write_pnm")
+
+
+def dense_scene(problem, intr, extr, X, wh, registered=None, pt_ok=None, keep_obs=None):
+    """sfm_dense_scene_build + get_info + fetch + destroy: the scene of
+    openMVG2openMVS as a dict of arrays: K [n_platforms, 3, 3], platform_wh,
+    image_src, image_platform, image_pose, R [n_images, 3, 3], C [n_images, 3],
+    vert_X (float32) [n_vertices, 3], vert_off, vert_view, vert_pt, n_short."""
+    lib = abi.load()
+    n_img, n_pt = problem.n_img, problem.n_pt
+    intr = np.ascontiguousarray(np.asarray(intr, np.float64).reshape(-1))
+    extr = np.ascontiguousarray(np.asarray(extr, np.float64).reshape(-1))
+    X = np.ascontiguousarray(np.asarray(X, np.float64).reshape(-1))
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    assert len(extr) == 6 * n_img and len(X) == 3 * n_pt and len(wh) == 2 * n_img
+    h = C.c_void_p()
+    _check(lib.sfm_dense_scene_build(C.byref(problem), abi.ptr(intr if len(intr) else np.zeros(1), abi.f64p),
+                                     abi.ptr(extr if n_img else np.zeros(6), abi.f64p),
+                                     abi.ptr(X if n_pt else np.zeros(3), abi.f64p),
+                                     abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p),
+                                     abi.ptr(_mask(registered, n_img), abi.u8p), abi.ptr(_mask(pt_ok, n_pt), abi.u8p),
+                                     abi.ptr(_mask(keep_obs, problem.n_obs), abi.u8p), C.byref(h)),
+           "sfm_dense_scene_build")
+    try:
+        info = abi.DenseSceneInfo()
+        _check(lib.sfm_dense_scene_get_info(h, C.byref(info)), "sfm_dense_scene_get_info")
+        npl, ni, nv, nw = info.n_platforms, info.n_images, info.n_vertices, info.n_views
+        out = dict(K=np.zeros((npl, 3, 3)), platform_wh=np.zeros((npl, 2), np.int32), image_src=np.zeros(ni, np.int32),
+                   image_platform=np.zeros(ni, np.int32), image_pose=np.zeros(ni, np.int32), R=np.zeros((ni, 3, 3)),
+                   C=np.zeros((ni, 3)), vert_X=np.zeros((nv, 3), np.float32), vert_off=np.zeros(nv + 1, np.int64),
+                   vert_view=np.zeros(nw, np.uint32), vert_pt=np.zeros(nv, np.int64))
+        types = dict(K=abi.f64p, platform_wh=abi.i32p, image_src=abi.i32p, image_platform=abi.i32p,
+                     image_pose=abi.i32p, R=abi.f64p, C=abi.f64p, vert_X=abi.f32p, vert_off=abi.i64p,
+                     vert_view=abi.u32p, vert_pt=abi.i64p)
+        _check(lib.sfm_dense_scene_fetch(h, *[abi.ptr(out[k], types[k]) if out[k].size else None for k in types]),
+               "sfm_dense_scene_fetch")
+        out["n_short"] = info.n_short
+        return out
+    finally:
+        lib.sfm_dense_scene_destroy(h)

@@ -17,6 +17,9 @@
 //   ColorizeTracks        OpenMVG's greedy track colouring, what colorize() runs
 //                         (colorize.hpp; sfm_colorize), and sparseBuilder::colorize()
 //                         file-staged
+//   UndistortImages, DenseBuilder  the dense hand-off: every image undistorted
+//                         (sfm_undistort) and the scene DenseBuilder::save()
+//                         collects (dense.hpp; sfm_dense_scene_*)
 //   SIFT_Image_describer  src/nonFree/sift/SIFT_describer.hpp and detectFeature()
 //                         (sparseBuilder.cpp:575-756) on 8-bit gray buffers
 //                         (sift.hpp; sfm_sift)
@@ -47,6 +50,7 @@
 #include "actuator.hpp"
 #include "adjuster.hpp"
 #include "colorize.hpp"
+#include "dense.hpp"
 #include "frames.hpp"
 #include "localizer.hpp"
 #include "reconstruction.hpp"
@@ -243,6 +247,27 @@ inline bool ColorizeTracks(const WorldStructure& world, const std::vector<Image:
                            Context& ctx = Context::thread_default(), const std::vector<uint8_t>* pt_ok = nullptr,
                            sfm_colorize_stats* stats = nullptr) {
     return ColorizeTracks(GpuColorizeBackend{&ctx}, world, images, pixels, colors, pt_ok, stats);
+}
+
+// ---------------------------------------------------------------------------
+// UndistortImages / DenseBuilder::exportUndistorted (dense.hpp) on the GPU: sfm_undistort
+// ---------------------------------------------------------------------------
+struct GpuUndistortBackend {
+    Context* ctx;
+    int undistort(int32_t camera_model, int32_t n_img, int32_t n_intr, const int32_t* img_intr, const double* intr,
+                  const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                  const sfm_undistort_opts* opts, uint8_t* out, sfm_undistort_stats* stats) const {
+        return sfm_undistort(ctx->get(), camera_model, n_img, n_intr, img_intr, intr, wh, channels, img_off, pixels, opts,
+                             out, stats);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+inline bool UndistortImages(int32_t camera_model, const std::vector<int32_t>& img_intr, const std::vector<double>& intr,
+                            const std::vector<ColorImage>& images, std::vector<std::vector<uint8_t>>& undistorted,
+                            Context& ctx = Context::thread_default(), const sfm_undistort_opts* opts = nullptr,
+                            sfm_undistort_stats* stats = nullptr) {
+    return UndistortImages(GpuUndistortBackend{&ctx}, camera_model, img_intr, intr, images, undistorted, opts, stats);
 }
 
 // ---------------------------------------------------------------------------

@@ -13,7 +13,7 @@ HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
      tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test tests/cpp/colorize_test \
-     tests/cpp/batch_points_test
+     tests/cpp/batch_points_test tests/cpp/undistort_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -99,3 +99,12 @@ tests/cpp/colorize_test: tests/cpp/colorize_test.cpp $(CSRC)/colorize.cpp $(HDRS
 # the Schur kernel's batch rule (csrc/ba_types.h batch_fits / batch_count) walked on the host
 tests/cpp/batch_points_test: tests/cpp/batch_points_test.cpp $(CSRC)/ba_types.h
 	g++ -O2 -std=c++17 -Wall -o $@ $<
+
+# the dense hand-off on the host backend: the host paths of csrc/undistort.cpp
+# (checks, chunk plan, host twin, PNM writer) and csrc/dense_scene.cpp and the
+# façade of include/sfm/dense.hpp compiled in (no library, no HIP runtime: host
+# only).  UNDISTORT_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
+UNDISTORT_HOST_SRCS := $(CSRC)/undistort.cpp $(CSRC)/dense_scene.cpp
+tests/cpp/undistort_test: tests/cpp/undistort_test.cpp $(UNDISTORT_HOST_SRCS) $(HDRS)
+	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas $(UNDISTORT_TEST_FLAGS) -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ \
+	    -I/opt/rocm/include -o $@ $< $(UNDISTORT_HOST_SRCS) -lpthread

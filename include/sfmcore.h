@@ -1550,6 +1550,140 @@ int sfm_sparse_reconstruct_colorize(sfm_ctx* ctx, const char* matches_dir, const
                                     const uint8_t* pixels, sfm_recon_stats* recon_stats,
                                     sfm_colorize_stats* color_stats);
 
+/* ------------------------------------------------------------------------ */
+/* Dense hand-off                                            */
+/* What denseWork() does before any MVS runs (OpenMVG's openMVG2openMVS      */
+/* export; src/denseBuilder/DenseBuilder.h:54-146 collects the same scene):  */
+/* every image is undistorted, and the scene (platforms with a               */
+/* distortion-free K, one image and pose per registered view, one vertex per */
+/* point seen in two or more of them) is collected.  The undistortion is     */
+/* per-pixel resampling of every image and runs on the device; the scene is  */
+/* integer work over the tracks and stays on the host.                       */
+/*                                                                          */
+/* Images: as sfm_colorize_sample reads them.  One byte pool `pixels`, image */
+/* i of wh[2i..] = (w, h) and channels[i] (1 or 3) starts at byte img_off[i] */
+/* (< 0: not loaded, skipped), row-major, interleaved, no row padding; the   */
+/* offsets need no alignment.  `out` has the same layout and offsets; bytes  */
+/* outside the loaded images are not touched.  Cameras: camera_model,        */
+/* img_intr[n_img], intr[iw*n_intr].                                         */
+/*   SFM_CAM_PINHOLE  no distortion: the image is a byte copy (OpenMVG       */
+/*                    copies the file).                                      */
+/*   SFM_CAM_RADIAL3  resampled whatever k1..k3 are (OpenMVG's have_disto()  */
+/*                    is a property of the class).                           */
+/*   SFM_CAM_SNAVELY  SFM_ERR_UNSUPPORTED: the BAL model has no principal    */
+/*                    point and so no raster origin.                         */
+/* Per pixel (OpenMVG's UndistortImage with Sampler2d<SamplerLinear>,        */
+/* restated from the published source).  For the output pixel (i, j) and     */
+/* {f, ppx, ppy, k1, k2, k3}, in double and in this order:                   */
+/*   px = (i - ppx) / f, py = (j - ppy) / f, r2 = px*px + py*py,             */
+/*   r4 = r2*r2, r6 = r4*r2, c = 1.0 + k1*r2 + k2*r4 + k3*r6,                */
+/*   x = f*(px*c) + ppx, y = f*(py*c) + ppy.                                 */
+/* The source is inside when x > -1.0 && x < w && y > -1.0 && y < h (NaN     */
+/* fails); otherwise the pixel is `fill`.  Inside: xf = (float)x,            */
+/* gx = floorf(xf), dx = (double)xf - (double)gx, likewise yf, gy, dy; the   */
+/* weights are {1 - dx, dx} and {1 - dy, dy}.  Over the rows gy, gy + 1      */
+/* (outer) and the columns gx, gx + 1 (inner), neighbours outside the image  */
+/* skipped: res += (double)pix * (wx*wy) per channel, total += wx*wy.        */
+/* total <= 0.2: the pixel is 0 in every channel (not `fill`).  Otherwise    */
+/* res /= total when total != 1.0, and the byte is (uint8_t)(res + 0.5).     */
+/* No operation is fused (csrc/undistort_point.h, one definition for the     */
+/* kernel and the host twin), so the device and the host twin give the same  */
+/* bytes and the same counts.                                                */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_undistort_opts {
+    int64_t chunk_bytes;     /* the device working set of one chunk (pitched
+                                input and output rows), so that a collection
+                                larger than device memory streams through;
+                                0: the library's default, 128 MiB.  Two chunks
+                                are resident at a time.  The result does not
+                                depend on it.                                  */
+    uint8_t fill[3];         /* the pixel whose source falls outside (0 0 0);
+                                a 1-channel image takes fill[0]                */
+    uint8_t reserved[5];
+} sfm_undistort_opts;
+/* [cpu] chunk_bytes 0, fill black */
+void sfm_undistort_default_options(sfm_undistort_opts* opts);
+typedef struct sfm_undistort_stats {
+    int64_t n_images;        /* loaded images (resampled or copied)            */
+    int64_t n_copied;        /* of those, byte copies (SFM_CAM_PINHOLE)        */
+    int64_t n_pixels;        /* output pixels of the resampled images          */
+    int64_t n_outside;       /* of those, the source fell outside: `fill`      */
+    int64_t n_low_weight;    /* of those, inside with total <= 0.2: 0          */
+    int32_t n_chunks;        /* chunks of the plan (the host twin reports the
+                                plan the device would run)                    */
+    int32_t reserved;
+    double seconds[3];       /* upload, kernels, download.  Device: summed over
+                                the chunks from stream events (chunks overlap,
+                                so the sum may exceed the wall time).  Host
+                                twin: 0, the resampling's wall time, 0.        */
+} sfm_undistort_stats;
+/* Every argument check runs on the host before any device call, and every
+ * violation is SFM_ERR_INVALID_ARG with a message: a non-positive image size,
+ * channels other than 1 or 3 on a loaded image, img_intr out of range, an
+ * unknown model, non-finite intrinsics or f == 0 on a block that a loaded
+ * image uses, a positive chunk_bytes too small for one output row of an image
+ * and the source rows it samples.  An image of 2^31 or more pixels is
+ * SFM_ERR_UNSUPPORTED.  Chunks split between images and, for an image larger
+ * than the budget, between rows (the source rows each band samples are worked
+ * out on the host with the same arithmetic).  n_img == 0, or nothing loaded,
+ * succeeds and writes nothing.  opts NULL = the defaults; stats may be NULL. */
+int sfm_undistort(sfm_ctx* ctx, int32_t camera_model, int32_t n_img, int32_t n_intr, const int32_t* img_intr,
+                  const double* intr, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                  const uint8_t* pixels, const sfm_undistort_opts* opts, uint8_t* out, sfm_undistort_stats* stats);
+/* [cpu] the host twin (threads over bands of rows): the same bytes and counts */
+int sfm_undistort_host(int32_t camera_model, int32_t n_img, int32_t n_intr, const int32_t* img_intr,
+                       const double* intr, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                       const uint8_t* pixels, const sfm_undistort_opts* opts, uint8_t* out,
+                       sfm_undistort_stats* stats);
+/* [cpu] one image as binary PNM: "P5" (channels 1) or "P6" (channels 3),
+ * maxval 255.  Needs no codec; image encoding otherwise stays outside the
+ * library. */
+int sfm_undistort_write_pnm(const char* path, int32_t w, int32_t h, int32_t channels, const uint8_t* bytes);
+
+/* The scene of openMVG2openMVS / DenseBuilder::save(), from what
+ * sfm_reconstruct returns: tracks (n_img, n_intr, n_pt, n_obs, pt_offsets,
+ * obs_img, img_intr, camera_model are read), intr[iw*n_intr], extr[6*n_img],
+ * X[3*n_pt], wh[2*n_img]; registered[n_img], pt_ok[n_pt], keep_obs[n_obs] may
+ * each be NULL: all.
+ *   platforms  one per intrinsics block, in block order, used or not.  K is
+ *              row-major: PINHOLE [fx 0 cx; 0 fy cy; 0 0 1], RADIAL3
+ *              [f 0 ppx; 0 f ppy; 0 0 1] (no distortion: the images are
+ *              undistorted), SNAVELY SFM_ERR_UNSUPPORTED.  platform_wh is the
+ *              size of the lowest-indexed image of the block (0 0: none);
+ *              images of one block with different sizes: SFM_ERR_INVALID_ARG.
+ *   images     the registered images in ascending index order get the scene
+ *              IDs 0, 1, ...: image_src (the index), image_platform,
+ *              image_pose (the rank among the registered images of its
+ *              platform), R = R(w) row-major, C = -R' t.
+ *   vertices   for each point with pt_ok, in point order: the scene IDs of
+ *              the registered images that hold a live observation of it, each
+ *              once, ascending.  Fewer than two: dropped and counted in
+ *              n_short.  vert_X is X as float, vert_pt the source point,
+ *              vert_off[n_vertices + 1] / vert_view[n_views] the lists (CSR).
+ * Non-finite X or extr on something kept, or non-finite intr:
+ * SFM_ERR_INVALID_ARG.  The OpenMVS .mvs archive is not written (DESIGN.md
+ * §10); these arrays are everything it holds for this step. */
+typedef struct sfm_dense_scene sfm_dense_scene;
+typedef struct sfm_dense_scene_info {
+    int32_t n_platforms, n_images;
+    int64_t n_vertices, n_views, n_short;
+} sfm_dense_scene_info;
+/* [cpu] */
+int sfm_dense_scene_build(const sfm_ba_problem* tracks, const double* intr, const double* extr, const double* X,
+                          const int32_t* wh, const uint8_t* registered, const uint8_t* pt_ok,
+                          const uint8_t* keep_obs, sfm_dense_scene** scene);
+/* [cpu] */
+int sfm_dense_scene_get_info(const sfm_dense_scene* scene, sfm_dense_scene_info* info);
+/* [cpu] fills each array that is non-NULL: K[9*n_platforms],
+ * platform_wh[2*n_platforms], image_src / image_platform / image_pose
+ * [n_images], R[9*n_images], C[3*n_images], vert_X[3*n_vertices],
+ * vert_off[n_vertices + 1], vert_view[n_views], vert_pt[n_vertices]. */
+int sfm_dense_scene_fetch(const sfm_dense_scene* scene, double* K, int32_t* platform_wh, int32_t* image_src,
+                          int32_t* image_platform, int32_t* image_pose, double* R, double* C, float* vert_X,
+                          int64_t* vert_off, uint32_t* vert_view, int64_t* vert_pt);
+/* [cpu] */
+int sfm_dense_scene_destroy(sfm_dense_scene* scene);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
