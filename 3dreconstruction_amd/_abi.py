@@ -320,6 +320,29 @@ class DenseSceneInfo(C.Structure):
                 ("n_views", C.c_int64), ("n_short", C.c_int64)]
 
 
+class DepthViewsOpts(C.Structure):
+    _fields_ = [("opt_angle", C.c_double), ("min_angle", C.c_double), ("max_scale", C.c_double),
+                ("range_margin", C.c_double), ("min_shared", C.c_int32), ("max_neighbors", C.c_int32)]
+
+
+class DepthmapOpts(C.Structure):
+    _fields_ = [("half_window", C.c_int32), ("iterations", C.c_int32), ("n_best", C.c_int32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("device_bytes", C.c_int64)]
+
+
+class DepthmapStats(C.Structure):
+    _fields_ = [("n_images", C.c_int64), ("n_estimated", C.c_int64), ("n_invalid", C.c_int64),
+                ("resident_bytes", C.c_int64), ("seconds", C.c_double * 3)]
+
+
+class DepthmapFilterOpts(C.Structure):
+    _fields_ = [("max_cost", C.c_float), ("rel_tol", C.c_float), ("min_consistent", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DepthmapFilterStats(C.Structure):
+    _fields_ = [("n_candidates", C.c_int64), ("n_kept", C.c_int64), ("seconds", C.c_double * 3)]
+
+
 class SparseFilterStats(C.Structure):
     _fields_ = [("n_pairs_in", C.c_int64), ("n_pairs_out", C.c_int64), ("n_matches_in", C.c_int64),
                 ("n_matches_out", C.c_int64)]
@@ -440,6 +463,20 @@ SIGNATURES = [
     ("sfm_dense_scene_fetch", C.c_int, [C.c_void_p, f64p, i32p, i32p, i32p, i32p, f64p, f64p, f32p, i64p, u32p,
                                         i64p]),
     ("sfm_dense_scene_destroy", C.c_int, [C.c_void_p]),
+    ("sfm_depth_views_default_options", None, [C.POINTER(DepthViewsOpts)]),
+    ("sfm_depth_views_select", C.c_int, [C.c_int32, C.c_int32, C.c_int64, f64p, i32p, f64p, f64p, f32p, i64p, u32p,
+                                         C.POINTER(DepthViewsOpts), i64p, i32p, f64p, f32p]),
+    ("sfm_depthmap_default_options", None, [C.POINTER(DepthmapOpts)]),
+    ("sfm_depthmap", C.c_int, [C.c_void_p, C.c_int32, i32p, i32p, i64p, u8p, f64p, f64p, f64p, i64p, i32p, f32p, f32p,
+                               f32p, C.POINTER(DepthmapOpts), f32p, f32p, f32p, C.POINTER(DepthmapStats)]),
+    ("sfm_depthmap_host", C.c_int, [C.c_int32, i32p, i32p, i64p, u8p, f64p, f64p, f64p, i64p, i32p, f32p, f32p, f32p,
+                                    C.POINTER(DepthmapOpts), f32p, f32p, f32p, C.POINTER(DepthmapStats)]),
+    ("sfm_depthmap_filter_default_options", None, [C.POINTER(DepthmapFilterOpts)]),
+    ("sfm_depthmap_filter", C.c_int, [C.c_void_p, C.c_int32, i32p, f64p, f64p, f64p, i64p, i32p, f32p, f32p,
+                                      C.POINTER(DepthmapFilterOpts), f32p, u8p, i64p, C.POINTER(DepthmapFilterStats)]),
+    ("sfm_depthmap_filter_host", C.c_int, [C.c_int32, i32p, f64p, f64p, f64p, i64p, i32p, f32p, f32p,
+                                           C.POINTER(DepthmapFilterOpts), f32p, u8p, i64p,
+                                           C.POINTER(DepthmapFilterStats)]),
     ("sfm_sift_options_default", None, [C.POINTER(SiftOptions)]),
     ("sfm_sift", C.c_int, [C.c_void_p, u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
                            f32p, u8p, i64p, C.POINTER(SiftSummary)]),

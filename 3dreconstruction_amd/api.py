@@ -1451,3 +1451,145 @@ def dense_scene(problem, intr, extr, X, wh, registered=None, pt_ok=None, keep_ob
         return out
     finally:
         lib.sfm_dense_scene_destroy(h)
+
+
+# ---- dense depth maps -----------------------------------------------------------------
+def depth_views_default_options():
+    o = abi.DepthViewsOpts()
+    abi.load().sfm_depth_views_default_options(C.byref(o))
+    return o
+
+
+def depth_views_select(scene, opts=None):
+    """sfm_depth_views_select over the dict of dense_scene(): dict(nb_off,
+    nb_view, nb_score, drange [n_images, 2] float32)."""
+    lib = abi.load()
+    o = opts if opts is not None else depth_views_default_options()
+    K = np.ascontiguousarray(np.asarray(scene["K"], np.float64).reshape(-1))
+    plat = np.ascontiguousarray(np.asarray(scene["image_platform"], np.int32).reshape(-1))
+    R = np.ascontiguousarray(np.asarray(scene["R"], np.float64).reshape(-1))
+    Cc = np.ascontiguousarray(np.asarray(scene["C"], np.float64).reshape(-1))
+    X = np.ascontiguousarray(np.asarray(scene["vert_X"], np.float32).reshape(-1))
+    off = np.ascontiguousarray(np.asarray(scene["vert_off"], np.int64).reshape(-1))
+    view = np.ascontiguousarray(np.asarray(scene["vert_view"], np.uint32).reshape(-1))
+    n_img, n_vert = len(plat), len(off) - 1
+    cap = max(n_img * max(o.max_neighbors, 0), 1)
+    nb_off, nb_view = np.zeros(n_img + 1, np.int64), np.zeros(cap, np.int32)
+    nb_score, drange = np.zeros(cap), np.zeros((max(n_img, 1), 2), np.float32)
+    one = np.zeros(9)
+    _check(lib.sfm_depth_views_select(len(K) // 9, n_img, n_vert, abi.ptr(K if len(K) else one, abi.f64p),
+                                      abi.ptr(plat if n_img else np.zeros(1, np.int32), abi.i32p),
+                                      abi.ptr(R if n_img else one, abi.f64p), abi.ptr(Cc if n_img else one, abi.f64p),
+                                      abi.ptr(X if n_vert else np.zeros(3, np.float32), abi.f32p), abi.ptr(off, abi.i64p),
+                                      abi.ptr(view if len(view) else np.zeros(1, np.uint32), abi.u32p), C.byref(o),
+                                      abi.ptr(nb_off, abi.i64p), abi.ptr(nb_view, abi.i32p), abi.ptr(nb_score, abi.f64p),
+                                      abi.ptr(drange, abi.f32p)), "sfm_depth_views_select")
+    n = int(nb_off[-1])
+    return dict(nb_off=nb_off, nb_view=nb_view[:n].copy(), nb_score=nb_score[:n].copy(), drange=drange[:n_img])
+
+
+def depthmap_default_options():
+    o = abi.DepthmapOpts()
+    abi.load().sfm_depthmap_default_options(C.byref(o))
+    return o
+
+
+def depthmap_filter_default_options():
+    o = abi.DepthmapFilterOpts()
+    abi.load().sfm_depthmap_filter_default_options(C.byref(o))
+    return o
+
+
+def _depth_cameras(wh, K, R, Cc, nb_off, nb_view):
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    n_img = len(wh) // 2
+    K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(-1))
+    R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1))
+    Cc = np.ascontiguousarray(np.asarray(Cc, np.float64).reshape(-1))
+    nb_off = np.ascontiguousarray(np.asarray(nb_off, np.int64).reshape(-1))
+    nb_view = np.ascontiguousarray(np.asarray(nb_view, np.int32).reshape(-1))
+    assert len(K) == 9 * n_img and len(R) == 9 * n_img and len(Cc) == 3 * n_img and len(nb_off) == n_img + 1
+    n_map = int((wh[0::2].astype(np.int64) * wh[1::2]).sum()) if n_img and (wh > 0).all() else 0
+    one = np.zeros(9)
+    ptrs = (abi.ptr(K if n_img else one, abi.f64p), abi.ptr(R if n_img else one, abi.f64p),
+            abi.ptr(Cc if n_img else one, abi.f64p), abi.ptr(nb_off, abi.i64p),
+            abi.ptr(nb_view if len(nb_view) else np.zeros(1, np.int32), abi.i32p))
+    keep = (wh, K, R, Cc, nb_off, nb_view, one)
+    return wh, n_img, n_map, ptrs, keep
+
+
+def _map_views(wh, arr, comps=1):
+    out, at = [], 0
+    for i in range(len(wh) // 2):
+        w, h = int(wh[2 * i]), int(wh[2 * i + 1])
+        v = arr[comps * at:comps * (at + w * h)]
+        out.append(v.reshape(h, w) if comps == 1 else v.reshape(h, w, comps))
+        at += w * h
+    return out
+
+
+def depthmap(ctx, wh, K, R, Cc, nb_off, nb_view, drange, images=None, opts=None, pool=None, init_depth=None,
+             init_normal=None):
+    """sfm_depthmap (ctx None: sfm_depthmap_host).  K, R [n_img, 3, 3], Cc
+    [n_img, 3]; images as in undistort(); init_depth / init_normal: flat
+    float32 arrays laid out as the maps.  dict(depth, normal, cost (flat),
+    depth_maps / normal_maps / cost_maps (views per image), stats)."""
+    lib = abi.load()
+    wh, n_img, n_map, cams, keep = _depth_cameras(wh, K, R, Cc, nb_off, nb_view)
+    channels, img_off, pixels = pool if pool is not None else _pixel_pool(images)
+    drange = np.ascontiguousarray(np.asarray(drange, np.float32).reshape(-1))
+    assert len(drange) == 2 * n_img
+    depth, normal, cost = (np.zeros(max(k * n_map, 1), np.float32) for k in (1, 3, 1))
+    if init_depth is not None:
+        init_depth = np.ascontiguousarray(np.asarray(init_depth, np.float32).reshape(-1))
+        assert len(init_depth) == n_map
+    if init_normal is not None:
+        init_normal = np.ascontiguousarray(np.asarray(init_normal, np.float32).reshape(-1))
+        assert len(init_normal) == 3 * n_map
+    st = abi.DepthmapStats()
+    args = (n_img, abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p), abi.ptr(channels, abi.i32p),
+            abi.ptr(img_off, abi.i64p), abi.ptr(pixels, abi.u8p), cams[0], cams[1], cams[2], cams[3], cams[4],
+            abi.ptr(drange if n_img else np.zeros(2, np.float32), abi.f32p), abi.ptr(init_depth, abi.f32p),
+            abi.ptr(init_normal, abi.f32p), C.byref(opts) if opts is not None else None, abi.ptr(depth, abi.f32p),
+            abi.ptr(normal, abi.f32p), abi.ptr(cost, abi.f32p), C.byref(st))
+    if ctx is None:
+        _check(lib.sfm_depthmap_host(*args), "sfm_depthmap_host")
+    else:
+        _check(lib.sfm_depthmap(ctx.h, *args), "sfm_depthmap")
+    depth, normal, cost = depth[:n_map], normal[:3 * n_map], cost[:n_map]
+    return dict(depth=depth, normal=normal, cost=cost, depth_maps=_map_views(wh, depth),
+                normal_maps=_map_views(wh, normal, 3), cost_maps=_map_views(wh, cost), stats=_struct_dict(st))
+
+
+def depthmap_host(wh, K, R, Cc, nb_off, nb_view, drange, images=None, opts=None, pool=None, init_depth=None,
+                  init_normal=None):
+    return depthmap(None, wh, K, R, Cc, nb_off, nb_view, drange, images, opts, pool, init_depth, init_normal)
+
+
+def depthmap_filter(ctx, wh, K, R, Cc, nb_off, nb_view, depth, cost, opts=None):
+    """sfm_depthmap_filter (ctx None: sfm_depthmap_filter_host) over the flat
+    maps of depthmap().  dict(depth (flat), n_agree (flat uint8), depth_maps,
+    counts [n_img, 2] (candidates, kept), stats)."""
+    lib = abi.load()
+    wh, n_img, n_map, cams, keep = _depth_cameras(wh, K, R, Cc, nb_off, nb_view)
+    depth = np.ascontiguousarray(np.asarray(depth, np.float32).reshape(-1))
+    cost = np.ascontiguousarray(np.asarray(cost, np.float32).reshape(-1))
+    assert len(depth) == len(cost) and (n_map == 0 or len(depth) == n_map)
+    out, agree = np.zeros(max(n_map, 1), np.float32), np.zeros(max(n_map, 1), np.uint8)
+    counts = np.zeros((max(n_img, 1), 2), np.int64)
+    st = abi.DepthmapFilterStats()
+    args = (n_img, abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p), cams[0], cams[1], cams[2], cams[3], cams[4],
+            abi.ptr(depth if n_map else np.zeros(1, np.float32), abi.f32p),
+            abi.ptr(cost if n_map else np.zeros(1, np.float32), abi.f32p), C.byref(opts) if opts is not None else None,
+            abi.ptr(out, abi.f32p), abi.ptr(agree, abi.u8p), abi.ptr(counts, abi.i64p), C.byref(st))
+    if ctx is None:
+        _check(lib.sfm_depthmap_filter_host(*args), "sfm_depthmap_filter_host")
+    else:
+        _check(lib.sfm_depthmap_filter(ctx.h, *args), "sfm_depthmap_filter")
+    out, agree = out[:n_map], agree[:n_map]
+    return dict(depth=out, n_agree=agree, depth_maps=_map_views(wh, out), counts=counts[:n_img],
+                stats=_struct_dict(st))
+
+
+def depthmap_filter_host(wh, K, R, Cc, nb_off, nb_view, depth, cost, opts=None):
+    return depthmap_filter(None, wh, K, R, Cc, nb_off, nb_view, depth, cost, opts)

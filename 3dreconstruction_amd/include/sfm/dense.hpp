@@ -10,6 +10,11 @@
 //                     WorldStructure: scene() returns the arrays that save() collects
 //                     (sfm_dense_scene_*), exportUndistorted() writes <stem>.pgm / .ppm.
 //                     The .mvs archive itself is not written.
+//   DepthMapEstimator the depth-map phase of DensifyPointCloud over a DenseScene and the
+//                     undistorted images: selectViews() (sfm_depth_views_select),
+//                     estimate() (sfm_depthmap), filter() (sfm_depthmap_filter), over a
+//                     backend policy with depthmap() and filter(); sfm.hpp binds it to
+//                     the GPU, HostDepthMapBackend is the host twin, with the same bytes.
 // Header-only.
 #pragma once
 #include <array>
@@ -232,6 +237,153 @@ class DenseBuilder {
     }
 
     const WorldStructure::Ptr structure_;
+};
+
+struct HostDepthMapBackend {
+    int depthmap(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                 const double* K, const double* R, const double* C, const int64_t* nb_off, const int32_t* nb_view,
+                 const float* drange, const float* init_depth, const float* init_normal, const sfm_depthmap_opts* opts,
+                 float* depth, float* normal, float* cost, sfm_depthmap_stats* stats) const {
+        return sfm_depthmap_host(n_img, wh, channels, img_off, pixels, K, R, C, nb_off, nb_view, drange, init_depth,
+                                 init_normal, opts, depth, normal, cost, stats);
+    }
+    int filter(int32_t n_img, const int32_t* wh, const double* K, const double* R, const double* C, const int64_t* nb_off,
+               const int32_t* nb_view, const float* depth, const float* cost, const sfm_depthmap_filter_opts* opts,
+               float* depth_out, uint8_t* n_agree, int64_t* counts, sfm_depthmap_filter_stats* stats) const {
+        return sfm_depthmap_filter_host(n_img, wh, K, R, C, nb_off, nb_view, depth, cost, opts, depth_out, n_agree, counts,
+                                        stats);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+
+// The depth-map phase over the scene's images (scene ID order; images[k] is the
+// undistorted image of scene image k, data null where it is not loaded).
+// selectViews() fills the neighbour lists and depth ranges (or set them
+// yourself), estimate() the maps, filter() the filtered depth.  Image k's maps
+// start at pixel map_off[k].  Every step returns false when its call failed.
+template <class Backend>
+class DepthMapEstimator {
+   public:
+    DepthMapEstimator(const Backend& backend, const DenseScene& scene, const std::vector<ColorImage>& images)
+        : backend_(backend), scene_(scene), images_(images) {
+        int64_t at = 0;
+        for (const auto& im : images_) {
+            map_off.push_back(at);
+            at += (int64_t)(im.w > 0 ? im.w : 0) * (im.h > 0 ? im.h : 0);
+        }
+        map_off.push_back(at);
+    }
+
+    bool selectViews(const sfm_depth_views_opts* opts = nullptr) {
+        sfm_depth_views_opts o;
+        sfm_depth_views_default_options(&o);
+        if (opts) o = *opts;
+        const size_t n = images_.size(), cap = n * (size_t)(o.max_neighbors > 0 ? o.max_neighbors : 0) + 1;
+        if (n != (size_t)scene_.info.n_images) return fail("selectViews", "the scene and the images differ in number", 0);
+        nb_off.assign(n + 1, 0);
+        nb_view.assign(cap, 0);
+        nb_score.assign(cap, 0.0);
+        drange.assign(2 * n + 2, 0.f);
+        const float none_x[3] = {0.f, 0.f, 0.f};
+        const uint32_t none_v = 0;
+        const int rc = sfm_depth_views_select(
+            scene_.info.n_platforms, scene_.info.n_images, scene_.info.n_vertices, scene_.K.data(),
+            scene_.image_platform.data(), scene_.R.data(), scene_.C.data(),
+            scene_.vert_X.empty() ? none_x : scene_.vert_X.data(), scene_.vert_off.data(),
+            scene_.vert_view.empty() ? &none_v : scene_.vert_view.data(), &o, nb_off.data(), nb_view.data(),
+            nb_score.data(), drange.data());
+        if (rc != SFM_OK) return fail("selectViews", sfm_last_error(), rc);
+        nb_view.resize((size_t)nb_off[n]);
+        nb_score.resize((size_t)nb_off[n]);
+        return true;
+    }
+
+    bool estimate(const sfm_depthmap_opts* opts = nullptr, const float* init_depth = nullptr,
+                  const float* init_normal = nullptr) {
+        const size_t n = images_.size(), n_map = (size_t)map_off.back();
+        if (nb_off.size() != n + 1 || drange.size() < 2 * n) return fail("estimate", "no neighbour lists: selectViews() first", 0);
+        cameras();
+        std::vector<int32_t> channels;
+        std::vector<int64_t> img_off;
+        std::vector<uint8_t> pool;
+        for (const auto& im : images_) {
+            channels.push_back(im.channels);
+            img_off.push_back(im.data ? (int64_t)pool.size() : -1);
+            if (im.data && im.w > 0 && im.h > 0 && im.channels > 0)
+                pool.insert(pool.end(), im.data, im.data + (size_t)im.w * im.h * im.channels);
+        }
+        pool.push_back(0);   // (never empty)
+        channels.push_back(1);
+        img_off.push_back(-1);
+        depth.assign(n_map + 1, 0.f);
+        normal.assign(3 * n_map + 1, 0.f);
+        cost.assign(n_map + 1, 0.f);
+        std::vector<int32_t> nbv(nb_view);
+        nbv.push_back(0);
+        const int rc = backend_.depthmap((int32_t)n, wh_.data(), channels.data(), img_off.data(), pool.data(), K_.data(),
+                                         scene_.R.data(), scene_.C.data(), nb_off.data(), nbv.data(), drange.data(),
+                                         init_depth, init_normal, opts, depth.data(), normal.data(), cost.data(), &stats);
+        if (rc != SFM_OK) return fail("estimate", backend_.last_error(), rc);
+        depth.resize(n_map);
+        normal.resize(3 * n_map);
+        cost.resize(n_map);
+        return true;
+    }
+
+    bool filter(const sfm_depthmap_filter_opts* opts = nullptr) {
+        const size_t n = images_.size(), n_map = (size_t)map_off.back();
+        if (depth.size() != n_map || cost.size() != n_map) return fail("filter", "no maps: estimate() first", 0);
+        cameras();
+        filtered.assign(n_map + 1, 0.f);
+        n_agree.assign(n_map + 1, 0);
+        counts.assign(2 * n + 2, 0);
+        std::vector<int32_t> nbv(nb_view);
+        nbv.push_back(0);
+        std::vector<float> d(depth), c(cost);
+        d.push_back(0.f);
+        c.push_back(0.f);
+        const int rc = backend_.filter((int32_t)n, wh_.data(), K_.data(), scene_.R.data(), scene_.C.data(), nb_off.data(),
+                                       nbv.data(), d.data(), c.data(), opts, filtered.data(), n_agree.data(),
+                                       counts.data(), &filter_stats);
+        if (rc != SFM_OK) return fail("filter", backend_.last_error(), rc);
+        filtered.resize(n_map);
+        n_agree.resize(n_map);
+        counts.resize(2 * n);
+        return true;
+    }
+
+    std::vector<int64_t> map_off, nb_off, counts;
+    std::vector<int32_t> nb_view;
+    std::vector<double> nb_score;
+    std::vector<float> drange, depth, normal, cost, filtered;
+    std::vector<uint8_t> n_agree;
+    sfm_depthmap_stats stats{};
+    sfm_depthmap_filter_stats filter_stats{};
+
+   private:
+    // K per image (the platform's) and the sizes, padded so that nothing is empty
+    void cameras() {
+        K_.clear();
+        wh_.clear();
+        for (size_t k = 0; k < images_.size(); ++k) {
+            const double* Kp = scene_.K.data() + 9 * (size_t)scene_.image_platform[k];
+            K_.insert(K_.end(), Kp, Kp + 9);
+            wh_.push_back(images_[k].w);
+            wh_.push_back(images_[k].h);
+        }
+        K_.resize(K_.size() + 9, 1.0);
+        wh_.resize(wh_.size() + 2, 1);
+    }
+    static bool fail(const char* step, const char* why, int rc) {
+        std::fprintf(stderr, "DepthMapEstimator::%s failed: %s (code %d)\n", step, why, rc);
+        return false;
+    }
+
+    const Backend backend_;
+    const DenseScene& scene_;
+    const std::vector<ColorImage> images_;
+    std::vector<double> K_;
+    std::vector<int32_t> wh_;
 };
 
 }  // namespace sfm

@@ -20,6 +20,9 @@
 //   UndistortImages, DenseBuilder  the dense hand-off: every image undistorted
 //                         (sfm_undistort) and the scene DenseBuilder::save()
 //                         collects (dense.hpp; sfm_dense_scene_*)
+//   DepthMapEstimator     the depth-map phase of DensifyPointCloud: view selection,
+//                         PatchMatch depth maps, the consistency filter (dense.hpp;
+//                         sfm_depth_views_select, sfm_depthmap, sfm_depthmap_filter)
 //   SIFT_Image_describer  src/nonFree/sift/SIFT_describer.hpp and detectFeature()
 //                         (sparseBuilder.cpp:575-756) on 8-bit gray buffers
 //                         (sift.hpp; sfm_sift)
@@ -269,6 +272,28 @@ inline bool UndistortImages(int32_t camera_model, const std::vector<int32_t>& im
                             sfm_undistort_stats* stats = nullptr) {
     return UndistortImages(GpuUndistortBackend{&ctx}, camera_model, img_intr, intr, images, undistorted, opts, stats);
 }
+
+// ---------------------------------------------------------------------------
+// DepthMapEstimator (dense.hpp) on the GPU: sfm_depthmap, sfm_depthmap_filter
+// ---------------------------------------------------------------------------
+struct GpuDepthMapBackend {
+    Context* ctx;
+    int depthmap(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                 const double* K, const double* R, const double* C, const int64_t* nb_off, const int32_t* nb_view,
+                 const float* drange, const float* init_depth, const float* init_normal, const sfm_depthmap_opts* opts,
+                 float* depth, float* normal, float* cost, sfm_depthmap_stats* stats) const {
+        return sfm_depthmap(ctx->get(), n_img, wh, channels, img_off, pixels, K, R, C, nb_off, nb_view, drange, init_depth,
+                            init_normal, opts, depth, normal, cost, stats);
+    }
+    int filter(int32_t n_img, const int32_t* wh, const double* K, const double* R, const double* C, const int64_t* nb_off,
+               const int32_t* nb_view, const float* depth, const float* cost, const sfm_depthmap_filter_opts* opts,
+               float* depth_out, uint8_t* n_agree, int64_t* counts, sfm_depthmap_filter_stats* stats) const {
+        return sfm_depthmap_filter(ctx->get(), n_img, wh, K, R, C, nb_off, nb_view, depth, cost, opts, depth_out, n_agree,
+                                   counts, stats);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+using GpuDepthMapEstimator = DepthMapEstimator<GpuDepthMapBackend>;
 
 // ---------------------------------------------------------------------------
 // SIFT_Image_describer (sift.hpp) on the GPU: sfm_sift

@@ -13,7 +13,7 @@ HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
      tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test tests/cpp/colorize_test \
-     tests/cpp/batch_points_test tests/cpp/undistort_test
+     tests/cpp/batch_points_test tests/cpp/undistort_test tests/cpp/depthmap_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -108,3 +108,13 @@ UNDISTORT_HOST_SRCS := $(CSRC)/undistort.cpp $(CSRC)/dense_scene.cpp
 tests/cpp/undistort_test: tests/cpp/undistort_test.cpp $(UNDISTORT_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas $(UNDISTORT_TEST_FLAGS) -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ \
 	    -I/opt/rocm/include -o $@ $< $(UNDISTORT_HOST_SRCS) -lpthread
+
+# the dense depth maps on the host backend: the host paths of csrc/depthmap.cpp
+# (checks, view selection, the host twins of the estimation and of the filter)
+# and csrc/dense_scene.cpp and the façade of include/sfm/dense.hpp compiled in
+# (no library, no HIP runtime: host only).
+# DEPTHMAP_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
+DEPTHMAP_HOST_SRCS := $(CSRC)/depthmap.cpp $(CSRC)/undistort.cpp $(CSRC)/dense_scene.cpp
+tests/cpp/depthmap_test: tests/cpp/depthmap_test.cpp $(DEPTHMAP_HOST_SRCS) $(HDRS)
+	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas $(DEPTHMAP_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY -DSFM_UNDISTORT_HOST_ONLY \
+	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(DEPTHMAP_HOST_SRCS) -lpthread

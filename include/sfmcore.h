@@ -1684,6 +1684,185 @@ int sfm_dense_scene_fetch(const sfm_dense_scene* scene, double* K, int32_t* plat
 /* [cpu] */
 int sfm_dense_scene_destroy(sfm_dense_scene* scene);
 
+/* ------------------------------------------------------------------------ */
+/* Dense depth maps                                          */
+/* The first half of denseWork()'s second command, DensifyPointCloud: which  */
+/* views each image is matched against, a depth and a normal per pixel by    */
+/* PatchMatch stereo on the device, and the cross-view consistency filter.   */
+/* OpenMVS is not available here, so nothing below is pinned to its numbers: */
+/* this comment is the contract.  The scheme is the red/black checkerboard   */
+/* PatchMatch of Gipuma / ACMH (the family OpenMVS's GPU path belongs to): a */
+/* pass updates the pixels of one colour from planes of the other colour     */
+/* only, so it has no races and no order, and the device, the host twin and  */
+/* a restatement give the same bytes.  Fusion, .dmap / .mvs files and the    */
+/* mesh stage are not built.                                                 */
+/*                                                                          */
+/* Images: n_img images laid out as sfm_undistort's `out` (wh, channels 1 or */
+/* 3, img_off < 0: not loaded, one byte pool).  A 3-channel pixel becomes    */
+/* gray by (77 r + 150 g + 29 b + 128) >> 8.  Cameras per image: K[9], R[9]  */
+/* row-major, C[3]: x = K R (X - C).  Neighbours: CSR nb_off[n_img + 1],     */
+/* nb_view (at most 8 per image); drange[2 i ..] = d_min, d_max (float).     */
+/* Maps: image i's maps start at pixel map_off(i) = the sum of w * h of the  */
+/* images before it, loaded or not: depth[n_map], normal[3 n_map],           */
+/* cost[n_map].  An image gets maps when it is loaded and has neighbours     */
+/* ("active"); every other image's maps are all zero.  In an active image    */
+/* the pixels at least r = half_window from every edge are estimated; the    */
+/* others are depth 0, normal 0 0 0, cost 2.                                 */
+/*                                                                          */
+/* All per-pixel arithmetic is float, every operation a single IEEE          */
+/* operation in the order written; a (x) b (+) c stands for two operations.  */
+/* dot(a, b) = (a0 b0 + a1 b1) + a2 b2.  M [x y 1] has the rows              */
+/* (M0 x + M1 y) + M2.  The host works out in double and rounds once, per    */
+/* image Ki = K^-1 and per (reference r, neighbour j)                        */
+/*   A = K_j R_j R_r' K_r^-1,  b = K_j R_j (C_r - C_j).                      */
+/* ray(q) = Ki [q 1].  imin = 1.0f / d_max, imax = 1.0f / d_min.             */
+/* Plane (d, n) at pixel p: t = dot(n, d * ray(p)) (d times each component). */
+/* For a patch pixel q: z = t / dot(n, ray(q)), a = A [q 1],                 */
+/* h = z * a + b (per component), x = h0 / h2, y = h1 / h2.  The sample is   */
+/* valid when z > 0, h2 > 0, 0 <= x <= w_j - 1, 0 <= y <= h_j - 1 (NaN       */
+/* fails).  x0 = floorf(x), fx = x - x0, x1 = min(x0 + 1, w_j - 1), likewise */
+/* y; top = g00 + fx * (g10 - g00), bot = g01 + fx * (g11 - g01),            */
+/* sample = top + fy * (bot - top).                                          */
+/* Cost against one neighbour: over the (2r+1)^2 = N patch, rows outer,      */
+/* columns inner, a = the reference's gray at the integer pixel, b = the     */
+/* sample: Sa += a, Sb += b, Saa += a a, Sbb += b b, Sab += a b.             */
+/* va = Saa - (Sa Sa) / N, vb = Sbb - (Sb Sb) / N, cov = Sab - (Sa Sb) / N.  */
+/* Any invalid sample, !(va >= N), !(vb >= N) or a neighbour that is not     */
+/* loaded: cost 2.  Otherwise c = cov / sqrtf(va * vb) clamped to [-1, 1]    */
+/* and cost = 1 - c.                                                         */
+/* Cost of a plane: the neighbours' costs ascending, the first               */
+/* m = min(n_best, n_nb) summed in that order, divided by (float)m.          */
+/* Random numbers: draw k of pixel idx = y w + x of image i is               */
+/*   u_k = (float)(mix64(entity_seed(seed, i, idx) + k * 0x9E3779B97F4A7C15) */
+/*                 >> 40) * 2^-24   (csrc/synth_rng.h's mix64, entity_seed). */
+/* Draws 0 1 2: the initial plane.  Iteration it (from 0) uses               */
+/* 3 + 7 it + {0: depth, 1 2 3: normal} for the perturbed plane and          */
+/* 3 + 7 it + {4 5 6} for the fresh random plane.                            */
+/* Random plane from (u, u', u''): inv = imin + u * (imax - imin),           */
+/* d = 1.0f / inv, n = (2 u' - 1, 2 u'' - 1, -1) divided by its length       */
+/* sqrtf((n0 n0 + n1 n1) + n2 n2), negated when dot(n, ray(p)) > 0.          */
+/* Init: the random plane, or the caller's (init_depth, init_normal, used    */
+/* as they are: a plane that is no plane costs 2); its cost.                 */
+/* Iteration it: the pixels with (x + y) & 1 == 0, then the others.  At an   */
+/* active pixel p with plane (d, n) and cost c:                              */
+/*   1. for the offsets (-1,0) (1,0) (0,-1) (0,1) (-5,0) (5,0) (0,-5) (0,5)  */
+/*      in this order, where p + offset = s is an estimated pixel: with s's  */
+/*      plane (d_s, n_s), d' = dot(n_s, d_s * ray(s)) / dot(n_s, ray(p));    */
+/*      skipped unless d_min <= d' <= d_max (NaN fails); the plane (d', n_s) */
+/*      replaces the current one when its cost is strictly lower.            */
+/*   2. delta = 0.1f / 2^it; inv = 1.0f / d + (delta * (2 u - 1)) * (imax -  */
+/*      imin) clamped to [imin, imax], d' = 1.0f / inv; n' = n + delta *     */
+/*      (2 u_c - 1) per component, divided by its length, facing rule as     */
+/*      above; taken when strictly lower.                                    */
+/*   3. a fresh random plane; taken when strictly lower.                     */
+/* No operation is fused (csrc/depthmap_point.h, one definition for the      */
+/* kernels and the host twin).                                               */
+/*                                                                          */
+/* View selection (after OpenMVS's published SelectNeighborViews, restated   */
+/* from memory: the weights and defaults are this library's design choices,  */
+/* not its numbers).  For image i and every other image j, over the vertices */
+/* seen in both, in double: theta = the angle at X between C_i - X and       */
+/* C_j - X in degrees; w_angle = min(theta / opt_angle, 1)^1.5;              */
+/* s = (f_i / z_i) / (f_j / z_j) with f = K[0] and z the depth of X in each  */
+/* camera; w_scale = s^2 if s < 1, (max_scale / s)^2 if s > max_scale, else  */
+/* 1; score(i, j) = the sum of w_angle * w_scale.  j is dropped when fewer   */
+/* than min_shared vertices are shared or the mean theta is below min_angle; */
+/* the rest sorted by score descending, ties to the lower index, at most     */
+/* max_neighbors (<= 8) kept.  drange = z_min / (1 + m), z_max * (1 + m)     */
+/* over the positive depths of the image's vertices, m = range_margin; an    */
+/* image without vertices or neighbours: an empty list and 0 0.              */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_depth_views_opts {
+    double opt_angle;        /* 10 degrees                                     */
+    double min_angle;        /* 3 degrees                                      */
+    double max_scale;        /* 1.6                                            */
+    double range_margin;     /* 0.25                                           */
+    int32_t min_shared;      /* 10                                             */
+    int32_t max_neighbors;   /* 4; at most 8                                   */
+} sfm_depth_views_opts;
+/* [cpu] */
+void sfm_depth_views_default_options(sfm_depth_views_opts* opts);
+/* [cpu] The arrays are sfm_dense_scene_fetch's.  nb_off[n_images + 1];
+ * nb_view and nb_score hold n_images * max_neighbors entries; drange
+ * [2 * n_images].  O(views * track length) on the host. */
+int sfm_depth_views_select(int32_t n_platforms, int32_t n_images, int64_t n_vertices, const double* K,
+                           const int32_t* image_platform, const double* R, const double* C, const float* vert_X,
+                           const int64_t* vert_off, const uint32_t* vert_view, const sfm_depth_views_opts* opts,
+                           int64_t* nb_off, int32_t* nb_view, double* nb_score, float* drange);
+
+typedef struct sfm_depthmap_opts {
+    int32_t half_window;     /* r: 3; 1..5                                     */
+    int32_t iterations;      /* 3; 0..16 (0: the initial planes' costs only)   */
+    int32_t n_best;          /* 2; at least 1                                  */
+    int32_t reserved;
+    uint64_t seed;
+    int64_t device_bytes;    /* budget for the resident images and maps;
+                                0: the library's default, 4 GiB               */
+} sfm_depthmap_opts;
+/* [cpu] */
+void sfm_depthmap_default_options(sfm_depthmap_opts* opts);
+typedef struct sfm_depthmap_stats {
+    int64_t n_images;        /* active images                                  */
+    int64_t n_estimated;     /* estimated pixels of those                      */
+    int64_t n_invalid;       /* of those, left at cost 2                       */
+    int64_t resident_bytes;  /* gray images, maps, views and pairs             */
+    double seconds[3];       /* upload, kernels, download (HIP events).  Host
+                                twin: 0, the estimation's wall time, 0.        */
+} sfm_depthmap_stats;
+/* Every check runs on the host before any device call.  SFM_ERR_INVALID_ARG
+ * with a message: a non-positive size, channels other than 1 or 3 on a loaded
+ * image, a neighbour index out of range or equal to the image itself, more
+ * than 8 neighbours, drange not 0 < d_min < d_max on an image with neighbours,
+ * a non-finite camera or a singular K, half_window outside 1..5, iterations
+ * outside 0..16, n_best < 1, only one of init_depth / init_normal.
+ * SFM_ERR_UNSUPPORTED: the resident set exceeds device_bytes (streaming is not
+ * built; the host twin refuses the same calls), an image of 2^31 or more
+ * pixels.  init_depth / init_normal (both or neither; laid out as depth /
+ * normal, and may be them) replace the random initial planes.  opts NULL = the
+ * defaults; stats may be NULL. */
+int sfm_depthmap(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                 const uint8_t* pixels, const double* K, const double* R, const double* C, const int64_t* nb_off,
+                 const int32_t* nb_view, const float* drange, const float* init_depth, const float* init_normal,
+                 const sfm_depthmap_opts* opts, float* depth, float* normal, float* cost, sfm_depthmap_stats* stats);
+/* [cpu] the host twin (threads over rows, pass after pass): the same bytes and counts */
+int sfm_depthmap_host(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                      const uint8_t* pixels, const double* K, const double* R, const double* C, const int64_t* nb_off,
+                      const int32_t* nb_view, const float* drange, const float* init_depth, const float* init_normal,
+                      const sfm_depthmap_opts* opts, float* depth, float* normal, float* cost,
+                      sfm_depthmap_stats* stats);
+
+/* The consistency filter.  It reads the unfiltered maps of all images, so the
+ * result does not depend on any order.  A pixel p with depth d > 0 and
+ * cost <= max_cost is a candidate.  For each neighbour j, in float:
+ * h = d * (A [p 1]) + b, z = h2, x = floorf(h0 / z + 0.5f), y likewise (the
+ * pixel rounded half up); j agrees when z > 0, 0 <= x <= w_j - 1,
+ * 0 <= y <= h_j - 1, depth_j(x, y) > 0 and |z - depth_j| <= rel_tol * z.  The
+ * candidate is kept when at least min(min_consistent, n_nb) neighbours agree.
+ * depth_out: the depth, or 0; n_agree: the agreeing neighbours of a candidate,
+ * else 0; counts[2 i ..] (may be NULL): candidates and kept pixels of image i.
+ * The checks on sizes, cameras and neighbours are sfm_depthmap's. */
+typedef struct sfm_depthmap_filter_opts {
+    float max_cost;          /* 0.5                                            */
+    float rel_tol;           /* 0.01                                           */
+    int32_t min_consistent;  /* 2                                              */
+    int32_t reserved;
+} sfm_depthmap_filter_opts;
+/* [cpu] */
+void sfm_depthmap_filter_default_options(sfm_depthmap_filter_opts* opts);
+typedef struct sfm_depthmap_filter_stats {
+    int64_t n_candidates, n_kept;
+    double seconds[3];       /* as sfm_depthmap_stats                          */
+} sfm_depthmap_filter_stats;
+int sfm_depthmap_filter(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const double* K, const double* R,
+                        const double* C, const int64_t* nb_off, const int32_t* nb_view, const float* depth,
+                        const float* cost, const sfm_depthmap_filter_opts* opts, float* depth_out, uint8_t* n_agree,
+                        int64_t* counts, sfm_depthmap_filter_stats* stats);
+/* [cpu] the host twin: the same bytes and counts */
+int sfm_depthmap_filter_host(int32_t n_img, const int32_t* wh, const double* K, const double* R, const double* C,
+                             const int64_t* nb_off, const int32_t* nb_view, const float* depth, const float* cost,
+                             const sfm_depthmap_filter_opts* opts, float* depth_out, uint8_t* n_agree,
+                             int64_t* counts, sfm_depthmap_filter_stats* stats);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
