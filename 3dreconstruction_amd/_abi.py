@@ -343,6 +343,25 @@ class DepthmapFilterStats(C.Structure):
     _fields_ = [("n_candidates", C.c_int64), ("n_kept", C.c_int64), ("seconds", C.c_double * 3)]
 
 
+class DepthmapFuseOpts(C.Structure):
+    _fields_ = [("rel_tol", C.c_float), ("min_normal_cos", C.c_float), ("device_bytes", C.c_int64)]
+
+
+class DepthmapFuseStats(C.Structure):
+    _fields_ = [("n_points", C.c_int64), ("n_suppressed", C.c_int64), ("n_pairs_dropped", C.c_int64),
+                ("resident_bytes", C.c_int64), ("seconds", C.c_double * 3)]
+
+
+class DensifyStats(C.Structure):
+    _fields_ = [("depthmap", DepthmapStats), ("filter", DepthmapFilterStats), ("fuse", DepthmapFuseStats),
+                ("seconds", C.c_double * 3)]
+
+
+# the fusion's limits (csrc/fuse_point.h)
+FUSE_MAX_PAIRS = 32
+FUSE_BLOCK = 256
+
+
 class SparseFilterStats(C.Structure):
     _fields_ = [("n_pairs_in", C.c_int64), ("n_pairs_out", C.c_int64), ("n_matches_in", C.c_int64),
                 ("n_matches_out", C.c_int64)]
@@ -366,6 +385,13 @@ def default_options():
 
 
 # (name, restype, argtypes) for every symbol declared in include/sfmcore.h
+# the argument groups of the fusion entry points
+_FUSE_IN = [C.c_int32, i32p, i32p, i64p, u8p, f64p, f64p, f64p, i64p, i32p, f32p, f32p, C.POINTER(DepthmapFuseOpts)]
+_CLOUD = [C.c_int64, f32p, f32p, u8p, u8p, u32p, i32p, i32p]
+_DENSIFY_IN = [C.c_int32, i32p, i32p, i64p, u8p, f64p, f64p, f64p, i64p, i32p, f32p, f32p, f32p,
+               C.POINTER(DepthmapOpts), C.POINTER(DepthmapFilterOpts), C.POINTER(DepthmapFuseOpts)]
+_DENSIFY_MAPS = [f32p, f32p, f32p, f32p, u8p, i64p]
+
 SIGNATURES = [
     ("sfm_version", C.c_char_p, []),
     ("sfm_last_error", C.c_char_p, []),
@@ -477,6 +503,13 @@ SIGNATURES = [
     ("sfm_depthmap_filter_host", C.c_int, [C.c_int32, i32p, f64p, f64p, f64p, i64p, i32p, f32p, f32p,
                                            C.POINTER(DepthmapFilterOpts), f32p, u8p, i64p,
                                            C.POINTER(DepthmapFilterStats)]),
+    ("sfm_depthmap_fuse_default_options", None, [C.POINTER(DepthmapFuseOpts)]),
+    ("sfm_depthmap_fuse", C.c_int, [C.c_void_p] + _FUSE_IN + _CLOUD + [C.POINTER(DepthmapFuseStats)]),
+    ("sfm_depthmap_fuse_host", C.c_int, _FUSE_IN + _CLOUD + [C.POINTER(DepthmapFuseStats)]),
+    ("sfm_dense_cloud_views", C.c_int, [C.c_int32, i64p, i32p, C.c_int64, i32p, u32p, i64p, i32p]),
+    ("sfm_dense_cloud_write_ply", C.c_int, [C.c_char_p, C.c_int64, f32p, f32p, u8p]),
+    ("sfm_densify", C.c_int, [C.c_void_p] + _DENSIFY_IN + _CLOUD + _DENSIFY_MAPS + [C.POINTER(DensifyStats)]),
+    ("sfm_densify_host", C.c_int, _DENSIFY_IN + _CLOUD + _DENSIFY_MAPS + [C.POINTER(DensifyStats)]),
     ("sfm_sift_options_default", None, [C.POINTER(SiftOptions)]),
     ("sfm_sift", C.c_int, [C.c_void_p, u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
                            f32p, u8p, i64p, C.POINTER(SiftSummary)]),

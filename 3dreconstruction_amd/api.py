@@ -1593,3 +1593,148 @@ def depthmap_filter(ctx, wh, K, R, Cc, nb_off, nb_view, depth, cost, opts=None):
 
 def depthmap_filter_host(wh, K, R, Cc, nb_off, nb_view, depth, cost, opts=None):
     return depthmap_filter(None, wh, K, R, Cc, nb_off, nb_view, depth, cost, opts)
+
+
+# ---- dense fusion ---------------------------------------------------------------------
+def depthmap_fuse_default_options():
+    o = abi.DepthmapFuseOpts()
+    abi.load().sfm_depthmap_fuse_default_options(C.byref(o))
+    return o
+
+
+def _cloud_arrays(cap, fill=0):
+    n = max(cap, 1)
+    return dict(X=np.full(3 * n, fill, np.float32), N=np.full(3 * n, fill, np.float32), rgb=np.full(3 * n, fill, np.uint8),
+                n_views=np.full(n, fill, np.uint8), view_mask=np.full(n, fill, np.uint32),
+                src_image=np.full(n, fill, np.int32), src_pixel=np.full(n, fill, np.int32))
+
+
+def _cloud_ptrs(cap, a):
+    return (cap, abi.ptr(a["X"], abi.f32p), abi.ptr(a["N"], abi.f32p), abi.ptr(a["rgb"], abi.u8p),
+            abi.ptr(a["n_views"], abi.u8p), abi.ptr(a["view_mask"], abi.u32p), abi.ptr(a["src_image"], abi.i32p),
+            abi.ptr(a["src_pixel"], abi.i32p))
+
+
+def _cloud_dict(a, n, colours, stats):
+    return dict(X=a["X"][:3 * n].reshape(-1, 3), N=a["N"][:3 * n].reshape(-1, 3),
+                rgb=a["rgb"][:3 * n].reshape(-1, 3) if colours else None, n_views=a["n_views"][:n],
+                view_mask=a["view_mask"][:n], src_image=a["src_image"][:n], src_pixel=a["src_pixel"][:n], stats=stats)
+
+
+def depthmap_fuse_raw(ctx, wh, K, R, Cc, nb_off, nb_view, depth, normal, images=None, opts=None, pool=None,
+                      cap_points=None, fill=0):
+    """sfm_depthmap_fuse (ctx None: sfm_depthmap_fuse_host) without the check of
+    its return code: (rc, the cloud's arrays at their full capacity, pre-filled
+    with `fill`, the stats dict).  cap_points None: the pixels with depth > 0."""
+    lib = abi.load()
+    wh, n_img, n_map, cams, keep = _depth_cameras(wh, K, R, Cc, nb_off, nb_view)
+    depth = np.ascontiguousarray(np.asarray(depth, np.float32).reshape(-1))
+    normal = np.ascontiguousarray(np.asarray(normal, np.float32).reshape(-1))
+    assert n_map == 0 or (len(depth) == n_map and len(normal) == 3 * n_map)
+    colours = images is not None or pool is not None
+    channels, img_off, pixels = (pool if pool is not None else _pixel_pool(images)) if colours else (None, None, None)
+    cap = int((depth[:n_map] > 0).sum()) if cap_points is None else int(cap_points)
+    arrays = _cloud_arrays(cap, fill)
+    st = abi.DepthmapFuseStats()
+    args = (n_img, abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p), abi.ptr(channels, abi.i32p),
+            abi.ptr(img_off, abi.i64p), abi.ptr(pixels, abi.u8p), cams[0], cams[1], cams[2], cams[3], cams[4],
+            abi.ptr(depth if n_map else np.zeros(1, np.float32), abi.f32p),
+            abi.ptr(normal if n_map else np.zeros(3, np.float32), abi.f32p),
+            C.byref(opts) if opts is not None else None) + _cloud_ptrs(cap, arrays) + (C.byref(st),)
+    rc = lib.sfm_depthmap_fuse_host(*args) if ctx is None else lib.sfm_depthmap_fuse(ctx.h, *args)
+    return rc, arrays, _struct_dict(st)
+
+
+def depthmap_fuse(ctx, wh, K, R, Cc, nb_off, nb_view, depth, normal, images=None, opts=None, pool=None):
+    """sfm_depthmap_fuse (ctx None: sfm_depthmap_fuse_host) over the filter's
+    depth and depthmap()'s normal (flat); images as in undistort(), None: no
+    colours.  dict(X, N [n, 3] float32, rgb [n, 3] uint8 or None, n_views
+    (uint8), view_mask (uint32), src_image, src_pixel (int32), stats)."""
+    rc, arrays, st = depthmap_fuse_raw(ctx, wh, K, R, Cc, nb_off, nb_view, depth, normal, images, opts, pool)
+    _check(rc, "sfm_depthmap_fuse_host" if ctx is None else "sfm_depthmap_fuse")
+    return _cloud_dict(arrays, st["n_points"], images is not None or pool is not None, st)
+
+
+def depthmap_fuse_host(wh, K, R, Cc, nb_off, nb_view, depth, normal, images=None, opts=None, pool=None):
+    return depthmap_fuse(None, wh, K, R, Cc, nb_off, nb_view, depth, normal, images, opts, pool)
+
+
+def densify(ctx, wh, K, R, Cc, nb_off, nb_view, drange, images=None, opts=None, filter_opts=None, fuse_opts=None,
+            pool=None, init_depth=None, init_normal=None, maps=True):
+    """sfm_densify (ctx None: sfm_densify_host): depth maps, filter and fusion in
+    one call.  The cloud as depthmap_fuse() returns it, plus, with maps=True,
+    depth, normal, cost, depth_filtered (flat float32), n_agree (uint8) and
+    counts [n_img, 2]; maps=False leaves the maps on the device."""
+    lib = abi.load()
+    wh, n_img, n_map, cams, keep = _depth_cameras(wh, K, R, Cc, nb_off, nb_view)
+    channels, img_off, pixels = pool if pool is not None else _pixel_pool(images)
+    drange = np.ascontiguousarray(np.asarray(drange, np.float32).reshape(-1))
+    assert len(drange) == 2 * n_img
+    if init_depth is not None:
+        init_depth = np.ascontiguousarray(np.asarray(init_depth, np.float32).reshape(-1))
+        assert len(init_depth) == n_map
+    if init_normal is not None:
+        init_normal = np.ascontiguousarray(np.asarray(init_normal, np.float32).reshape(-1))
+        assert len(init_normal) == 3 * n_map
+    arrays = _cloud_arrays(n_map)
+    m = dict(depth=np.zeros(max(n_map, 1), np.float32), normal=np.zeros(max(3 * n_map, 1), np.float32),
+             cost=np.zeros(max(n_map, 1), np.float32), depth_filtered=np.zeros(max(n_map, 1), np.float32),
+             n_agree=np.zeros(max(n_map, 1), np.uint8), counts=np.zeros((max(n_img, 1), 2), np.int64)) if maps else {}
+    st = abi.DensifyStats()
+    opt = lambda o: C.byref(o) if o is not None else None
+    args = (n_img, abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p), abi.ptr(channels, abi.i32p),
+            abi.ptr(img_off, abi.i64p), abi.ptr(pixels, abi.u8p), cams[0], cams[1], cams[2], cams[3], cams[4],
+            abi.ptr(drange if n_img else np.zeros(2, np.float32), abi.f32p), abi.ptr(init_depth, abi.f32p),
+            abi.ptr(init_normal, abi.f32p), opt(opts), opt(filter_opts), opt(fuse_opts)) + _cloud_ptrs(n_map, arrays) + (
+            abi.ptr(m.get("depth"), abi.f32p), abi.ptr(m.get("normal"), abi.f32p), abi.ptr(m.get("cost"), abi.f32p),
+            abi.ptr(m.get("depth_filtered"), abi.f32p), abi.ptr(m.get("n_agree"), abi.u8p),
+            abi.ptr(m.get("counts"), abi.i64p), C.byref(st))
+    if ctx is None:
+        _check(lib.sfm_densify_host(*args), "sfm_densify_host")
+    else:
+        _check(lib.sfm_densify(ctx.h, *args), "sfm_densify")
+    sd = _struct_dict(st)
+    out = _cloud_dict(arrays, sd["fuse"]["n_points"], True, sd)
+    if maps:
+        out.update(depth=m["depth"][:n_map], normal=m["normal"][:3 * n_map], cost=m["cost"][:n_map],
+                   depth_filtered=m["depth_filtered"][:n_map], n_agree=m["n_agree"][:n_map], counts=m["counts"][:n_img])
+    return out
+
+
+def densify_host(wh, K, R, Cc, nb_off, nb_view, drange, images=None, opts=None, filter_opts=None, fuse_opts=None,
+                 pool=None, init_depth=None, init_normal=None, maps=True):
+    return densify(None, wh, K, R, Cc, nb_off, nb_view, drange, images, opts, filter_opts, fuse_opts, pool, init_depth,
+                   init_normal, maps)
+
+
+def dense_cloud_views(n_img, nb_off, nb_view, src_image, view_mask):
+    """sfm_dense_cloud_views: (view_off [n + 1] int64, view_idx int32), the
+    images that see each point: its own first, then its agreeing fusion pairs."""
+    lib = abi.load()
+    nb_off = np.ascontiguousarray(np.asarray(nb_off, np.int64).reshape(-1))
+    nb_view = np.ascontiguousarray(np.asarray(nb_view, np.int32).reshape(-1))
+    src = np.ascontiguousarray(np.asarray(src_image, np.int32).reshape(-1))
+    mask = np.ascontiguousarray(np.asarray(view_mask, np.uint32).reshape(-1))
+    n = len(src)
+    assert len(mask) == n and len(nb_off) == n_img + 1
+    off = np.zeros(n + 1, np.int64)
+    args = (n_img, abi.ptr(nb_off, abi.i64p), abi.ptr(nb_view if len(nb_view) else np.zeros(1, np.int32), abi.i32p), n,
+            abi.ptr(src if n else np.zeros(1, np.int32), abi.i32p), abi.ptr(mask if n else np.zeros(1, np.uint32), abi.u32p),
+            abi.ptr(off, abi.i64p))
+    _check(lib.sfm_dense_cloud_views(*args, None), "sfm_dense_cloud_views")
+    idx = np.zeros(max(int(off[-1]), 1), np.int32)
+    _check(lib.sfm_dense_cloud_views(*args, abi.ptr(idx, abi.i32p)), "sfm_dense_cloud_views")
+    return off, idx[:int(off[-1])]
+
+
+def dense_cloud_write_ply(path, X, N=None, rgb=None):
+    """sfm_dense_cloud_write_ply: binary little-endian x y z [nx ny nz] [red green blue]"""
+    X = np.ascontiguousarray(np.asarray(X, np.float32).reshape(-1, 3))
+    n = len(X)
+    N = None if N is None else np.ascontiguousarray(np.asarray(N, np.float32).reshape(-1, 3))
+    rgb = None if rgb is None else np.ascontiguousarray(np.asarray(rgb, np.uint8).reshape(-1, 3))
+    assert (N is None or len(N) == n) and (rgb is None or len(rgb) == n)
+    pad = lambda a, t: a if a is None or n else np.zeros(3, t)
+    _check(abi.load().sfm_dense_cloud_write_ply(_b(path), n, abi.ptr(X if n else np.zeros(3, np.float32), abi.f32p),
+                                               abi.ptr(pad(N, np.float32), abi.f32p), abi.ptr(pad(rgb, np.uint8), abi.u8p)),
+           "sfm_dense_cloud_write_ply")

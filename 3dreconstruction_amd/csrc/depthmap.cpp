@@ -19,12 +19,10 @@
 
 using namespace sfm;
 
-namespace {
-
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
+namespace sfm {
 
 // fn(item) for every item in [0, n), on up to 16 threads; returns when all are done
-void parallel_for(size_t n, const std::function<void(size_t)>& fn) {
+void depth_parallel_for(size_t n, const std::function<void(size_t)>& fn) {
     std::atomic<size_t> next{0};
     auto work = [&] {
         for (size_t at; (at = next.fetch_add(1)) < n;) fn(at);
@@ -37,11 +35,11 @@ void parallel_for(size_t n, const std::function<void(size_t)>& fn) {
     for (auto& t : pool) t.join();
 }
 
-void mul33(const double* a, const double* b, double* o) {
+static void mul33(const double* a, const double* b, double* o) {
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) o[3 * r + c] = a[3 * r] * b[c] + a[3 * r + 1] * b[3 + c] + a[3 * r + 2] * b[6 + c];
 }
-bool inv33(const double* m, double* o) {
+static bool inv33(const double* m, double* o) {
     const double c0 = m[4] * m[8] - m[5] * m[7], c1 = m[5] * m[6] - m[3] * m[8], c2 = m[3] * m[7] - m[4] * m[6];
     const double det = m[0] * c0 + m[1] * c1 + m[2] * c2;
     if (!std::isfinite(det) || det == 0.0) return false;
@@ -57,18 +55,24 @@ bool inv33(const double* m, double* o) {
     return true;
 }
 
-struct Cameras {
-    int32_t n_img;
-    const int32_t* wh;
-    const double *K, *R, *C;
-    const int64_t* nb_off;
-    const int32_t* nb_view;
-};
+// A = K_j R_j R_i' K_i^-1, b = K_j R_j (C_i - C_j): in double, rounded once
+void depth_pair_matrices(const DepthCameras& m, int32_t i, int32_t j, float* A_out, float* b_out) {
+    double Kinv[9] = {}, Rt[9], KR[9], T[9], A[9];
+    inv33(m.K + 9 * i, Kinv);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Rt[3 * r + c] = m.R[9 * i + 3 * c + r];
+    mul33(m.K + 9 * j, m.R + 9 * j, KR);
+    mul33(KR, Rt, T);
+    mul33(T, Kinv, A);
+    const double dc[3] = {m.C[3 * i] - m.C[3 * j], m.C[3 * i + 1] - m.C[3 * j + 1], m.C[3 * i + 2] - m.C[3 * j + 2]};
+    for (int a = 0; a < 9; ++a) A_out[a] = (float)A[a];
+    for (int r = 0; r < 3; ++r) b_out[r] = (float)(KR[3 * r] * dc[0] + KR[3 * r + 1] * dc[1] + KR[3 * r + 2] * dc[2]);
+}
 
 // The checks that the estimation and the filter share, and the views and pairs
 // of the call.  channels / img_off / drange NULL: the filter (every image counts
 // as loaded, no ranges).
-void build_problem(const char* who, const Cameras& m, const int32_t* channels, const int64_t* img_off,
+void depth_build_problem(const char* who, const DepthCameras& m, const int32_t* channels, const int64_t* img_off,
                    const uint8_t* pixels, const float* drange, DepthProblem& P) {
     SFM_REQUIRE(m.n_img >= 0, SFM_ERR_INVALID_ARG, "%s: negative n_img", who);
     P.n_img = m.n_img;
@@ -133,18 +137,9 @@ void build_problem(const char* who, const Cameras& m, const int32_t* channels, c
             const int32_t j = m.nb_view[q];
             SFM_REQUIRE(j >= 0 && j < m.n_img && j != i, SFM_ERR_INVALID_ARG,
                         "%s: image %d names the neighbour %d (of %d images, itself excluded)", who, i, j, m.n_img);
-            // A = K_j R_j R_i' K_i^-1, b = K_j R_j (C_i - C_j)
-            double Rt[9], KR[9], T[9], A[9];
-            for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 3; ++c) Rt[3 * r + c] = m.R[9 * i + 3 * c + r];
-            mul33(m.K + 9 * j, m.R + 9 * j, KR);
-            mul33(KR, Rt, T);
-            mul33(T, &Kinv[9 * (size_t)i], A);
-            const double dc[3] = {m.C[3 * i] - m.C[3 * j], m.C[3 * i + 1] - m.C[3 * j + 1], m.C[3 * i + 2] - m.C[3 * j + 2]};
             DepthPair& Q = P.pairs[(size_t)q];
             std::memset(&Q, 0, sizeof Q);
-            for (int a = 0; a < 9; ++a) Q.A[a] = (float)A[a];
-            for (int r = 0; r < 3; ++r) Q.b[r] = (float)(KR[3 * r] * dc[0] + KR[3 * r + 1] * dc[1] + KR[3 * r + 2] * dc[2]);
+            depth_pair_matrices(m, i, j, Q.A, Q.b);
             const DepthView& J = P.views[(size_t)j];
             Q.view = j;
             Q.w = J.w;
@@ -159,7 +154,7 @@ void build_problem(const char* who, const Cameras& m, const int32_t* channels, c
     std::vector<int32_t> loaded;
     for (int32_t i = 0; i < m.n_img; ++i)
         if (P.views[(size_t)i].gray_off >= 0) loaded.push_back(i);
-    parallel_for(loaded.size(), [&](size_t at) {
+    depth_parallel_for(loaded.size(), [&](size_t at) {
         const int32_t i = loaded[at];
         const DepthView& V = P.views[(size_t)i];
         const uint8_t* src = pixels + img_off[i];
@@ -173,6 +168,70 @@ void build_problem(const char* who, const Cameras& m, const int32_t* channels, c
             dst[p] = (uint8_t)((77u * src[3 * p] + 150u * src[3 * p + 1] + 29u * src[3 * p + 2] + 128u) >> 8);
     });
 }
+
+// sfm_depthmap's checks (all but the output pointers), and what the call works on
+void depth_prepare(const char* who, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                   const uint8_t* pixels, const double* K, const double* R, const double* C, const int64_t* nb_off,
+                   const int32_t* nb_view, const float* drange, const float* init_depth, const float* init_normal,
+                   const sfm_depthmap_opts* opts, DepthCall& call) {
+    sfm_depthmap_opts o;
+    sfm_depthmap_default_options(&o);
+    if (opts) o = *opts;
+    SFM_REQUIRE(o.half_window >= 1 && o.half_window <= kDepthMaxHalfWindow, SFM_ERR_INVALID_ARG,
+                "%s: half_window %d is outside 1..%d", who, o.half_window, kDepthMaxHalfWindow);
+    SFM_REQUIRE(o.iterations >= 0 && o.iterations <= kDepthMaxIterations, SFM_ERR_INVALID_ARG,
+                "%s: iterations %d is outside 0..%d", who, o.iterations, kDepthMaxIterations);
+    SFM_REQUIRE(o.n_best >= 1, SFM_ERR_INVALID_ARG, "%s: n_best %d is not positive", who, o.n_best);
+    SFM_REQUIRE(o.device_bytes >= 0, SFM_ERR_INVALID_ARG, "%s: negative device_bytes", who);
+    SFM_REQUIRE(n_img <= 0 || (channels && img_off && drange), SFM_ERR_INVALID_ARG, "%s: null argument", who);
+    SFM_REQUIRE(!init_depth == !init_normal, SFM_ERR_INVALID_ARG, "%s: init_depth and init_normal go together", who);
+    DepthProblem& P = call.P;
+    depth_build_problem(who, DepthCameras{n_img, wh, K, R, C, nb_off, nb_view}, channels, img_off, pixels, drange, P);
+    sfm_depthmap_stats& st = call.st;
+    std::memset(&st, 0, sizeof st);
+    for (const DepthView& V : P.views) st.n_images += V.active;
+    // what the device holds: the gray pool, the five floats of every map pixel, the views and pairs
+    st.resident_bytes = (int64_t)P.gray.size() + 5 * (int64_t)sizeof(float) * P.n_map +
+                        (int64_t)(P.views.size() * sizeof(DepthView) + P.pairs.size() * sizeof(DepthPair));
+    const int64_t budget = o.device_bytes > 0 ? o.device_bytes : kDepthDefaultDeviceBytes;
+    SFM_REQUIRE(st.resident_bytes <= budget, SFM_ERR_UNSUPPORTED,
+                "%s: the images and maps need %lld resident bytes, device_bytes is %lld (streaming is not built)", who,
+                (long long)st.resident_bytes, (long long)budget);
+    call.prm = DepthParams{o.half_window, o.iterations, o.n_best, 0, o.seed};
+}
+
+// sfm_depthmap_filter's option check
+void depth_filter_prepare(const char* who, const sfm_depthmap_filter_opts* opts, DepthFilterParams& prm) {
+    sfm_depthmap_filter_opts o;
+    sfm_depthmap_filter_default_options(&o);
+    if (opts) o = *opts;
+    SFM_REQUIRE(o.max_cost >= 0.0f && o.rel_tol >= 0.0f && o.min_consistent >= 0, SFM_ERR_INVALID_ARG,
+                "%s: max_cost, rel_tol or min_consistent is negative or not a number", who);
+    prm = DepthFilterParams{o.max_cost, o.rel_tol, o.min_consistent, 0};
+}
+
+// the initial state of the maps on the host: images without maps of their own
+// are all zero; the others start from the caller's planes
+void depth_init_maps(const DepthProblem& P, const float* init_depth, const float* init_normal, float* depth,
+                     float* normal, float* cost) {
+    for (const DepthView& V : P.views) {
+        const size_t n = (size_t)V.w * V.h, at = (size_t)V.map_off;
+        if (V.active && init_depth) {
+            std::memmove(depth + at, init_depth + at, n * sizeof(float));
+            std::memmove(normal + 3 * at, init_normal + 3 * at, 3 * n * sizeof(float));
+        } else if (!V.active) {
+            std::memset(depth + at, 0, n * sizeof(float));
+            std::memset(normal + 3 * at, 0, 3 * n * sizeof(float));
+            if (cost) std::memset(cost + at, 0, n * sizeof(float));
+        }
+    }
+}
+
+}  // namespace sfm
+
+namespace {
+
+double seconds_now() { return PhaseTimer::now() * 1e-3; }
 
 // rows of the active images, one item each
 struct RowItem {
@@ -197,7 +256,7 @@ void depthmap_host(const DepthProblem& P, const DepthParams& prm, bool init_give
         n = normal + 3 * V.map_off;
         c = cost + V.map_off;
     };
-    parallel_for(items.size(), [&](size_t at) {
+    depth_parallel_for(items.size(), [&](size_t at) {
         const DepthView& V = P.views[(size_t)items[at].img];
         const DepthRef ref{gray + V.gray_off, V.w, 0, 0};
         const int32_t y = items[at].y;
@@ -216,7 +275,7 @@ void depthmap_host(const DepthProblem& P, const DepthParams& prm, bool init_give
     });
     for (int32_t it = 0; it < prm.iterations; ++it)
         for (int32_t colour = 0; colour < 2; ++colour)
-            parallel_for(items.size(), [&](size_t at) {
+            depth_parallel_for(items.size(), [&](size_t at) {
                 const DepthView& V = P.views[(size_t)items[at].img];
                 const DepthRef ref{gray + V.gray_off, V.w, 0, 0};
                 const int32_t y = items[at].y;
@@ -244,7 +303,7 @@ void filter_host(const DepthProblem& P, const DepthFilterParams& prm, const floa
     const std::vector<RowItem> items = rows_of(P, false);
     std::vector<std::atomic<int64_t>> acc((size_t)2 * P.n_img);
     for (auto& a : acc) a = 0;
-    parallel_for(items.size(), [&](size_t at) {
+    depth_parallel_for(items.size(), [&](size_t at) {
         const int32_t i = items[at].img, y = items[at].y;
         const DepthView& V = P.views[(size_t)i];
         const int32_t need = std::min(prm.min_consistent, V.nb1 - V.nb0);
@@ -270,45 +329,14 @@ int depthmap(const char* who, sfm_ctx* ctx, bool device, int32_t n_img, const in
              const float* init_normal, const sfm_depthmap_opts* opts, float* depth, float* normal, float* cost,
              sfm_depthmap_stats* stats) {
     SFM_REQUIRE(!device || ctx, SFM_ERR_INVALID_ARG, "%s: null context", who);
-    sfm_depthmap_opts o;
-    sfm_depthmap_default_options(&o);
-    if (opts) o = *opts;
-    SFM_REQUIRE(o.half_window >= 1 && o.half_window <= kDepthMaxHalfWindow, SFM_ERR_INVALID_ARG,
-                "%s: half_window %d is outside 1..%d", who, o.half_window, kDepthMaxHalfWindow);
-    SFM_REQUIRE(o.iterations >= 0 && o.iterations <= kDepthMaxIterations, SFM_ERR_INVALID_ARG,
-                "%s: iterations %d is outside 0..%d", who, o.iterations, kDepthMaxIterations);
-    SFM_REQUIRE(o.n_best >= 1, SFM_ERR_INVALID_ARG, "%s: n_best %d is not positive", who, o.n_best);
-    SFM_REQUIRE(o.device_bytes >= 0, SFM_ERR_INVALID_ARG, "%s: negative device_bytes", who);
-    SFM_REQUIRE(n_img <= 0 || (channels && img_off && drange), SFM_ERR_INVALID_ARG, "%s: null argument", who);
-    SFM_REQUIRE(!init_depth == !init_normal, SFM_ERR_INVALID_ARG, "%s: init_depth and init_normal go together", who);
-    DepthProblem P;
-    build_problem(who, Cameras{n_img, wh, K, R, C, nb_off, nb_view}, channels, img_off, pixels, drange, P);
+    DepthCall call;
+    depth_prepare(who, n_img, wh, channels, img_off, pixels, K, R, C, nb_off, nb_view, drange, init_depth, init_normal,
+                  opts, call);
+    const DepthProblem& P = call.P;
+    const DepthParams& prm = call.prm;
+    sfm_depthmap_stats& st = call.st;
     SFM_REQUIRE(P.n_map == 0 || (depth && normal && cost), SFM_ERR_INVALID_ARG, "%s: null output", who);
-    sfm_depthmap_stats st;
-    std::memset(&st, 0, sizeof st);
-    for (const DepthView& V : P.views) st.n_images += V.active;
-    // what the device holds: the gray pool, the five floats of every map pixel, the views and pairs
-    st.resident_bytes = (int64_t)P.gray.size() + 5 * (int64_t)sizeof(float) * P.n_map +
-                        (int64_t)(P.views.size() * sizeof(DepthView) + P.pairs.size() * sizeof(DepthPair));
-    const int64_t budget = o.device_bytes > 0 ? o.device_bytes : kDepthDefaultDeviceBytes;
-    SFM_REQUIRE(st.resident_bytes <= budget, SFM_ERR_UNSUPPORTED,
-                "%s: the images and maps need %lld resident bytes, device_bytes is %lld (streaming is not built)", who,
-                (long long)st.resident_bytes, (long long)budget);
-    const DepthParams prm{o.half_window, o.iterations, o.n_best, 0, o.seed};
-    if (P.n_map > 0) {
-        // images without maps of their own are all zero; the others start from the caller's planes
-        for (const DepthView& V : P.views) {
-            const size_t n = (size_t)V.w * V.h, at = (size_t)V.map_off;
-            if (V.active && init_depth) {
-                std::memmove(depth + at, init_depth + at, n * sizeof(float));
-                std::memmove(normal + 3 * at, init_normal + 3 * at, 3 * n * sizeof(float));
-            } else if (!V.active) {
-                std::memset(depth + at, 0, n * sizeof(float));
-                std::memset(normal + 3 * at, 0, 3 * n * sizeof(float));
-                std::memset(cost + at, 0, n * sizeof(float));
-            }
-        }
-    }
+    if (P.n_map > 0) depth_init_maps(P, init_depth, init_normal, depth, normal, cost);
     if (st.n_images > 0) {
         if (device) {
 #ifndef SFM_DEPTHMAP_HOST_ONLY
@@ -330,17 +358,13 @@ int depthmap_filter(const char* who, sfm_ctx* ctx, bool device, int32_t n_img, c
                     const float* cost, const sfm_depthmap_filter_opts* opts, float* depth_out, uint8_t* n_agree,
                     int64_t* counts, sfm_depthmap_filter_stats* stats) {
     SFM_REQUIRE(!device || ctx, SFM_ERR_INVALID_ARG, "%s: null context", who);
-    sfm_depthmap_filter_opts o;
-    sfm_depthmap_filter_default_options(&o);
-    if (opts) o = *opts;
-    SFM_REQUIRE(o.max_cost >= 0.0f && o.rel_tol >= 0.0f && o.min_consistent >= 0, SFM_ERR_INVALID_ARG,
-                "%s: max_cost, rel_tol or min_consistent is negative or not a number", who);
+    DepthFilterParams prm;
+    depth_filter_prepare(who, opts, prm);
     DepthProblem P;
-    build_problem(who, Cameras{n_img, wh, K, R, C, nb_off, nb_view}, nullptr, nullptr, nullptr, nullptr, P);
+    depth_build_problem(who, DepthCameras{n_img, wh, K, R, C, nb_off, nb_view}, nullptr, nullptr, nullptr, nullptr, P);
     SFM_REQUIRE(P.n_map == 0 || (depth && cost && depth_out && n_agree), SFM_ERR_INVALID_ARG, "%s: null argument", who);
     sfm_depthmap_filter_stats st;
     std::memset(&st, 0, sizeof st);
-    const DepthFilterParams prm{o.max_cost, o.rel_tol, o.min_consistent, 0};
     std::vector<int64_t> cnt((size_t)2 * std::max(n_img, 1), 0);
     if (P.n_map > 0) {
         if (device) {

@@ -3,6 +3,7 @@
 // depthmap.hip (the kernels and the launches) share.
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 #include "common.h"
@@ -34,7 +35,63 @@ struct DepthProblem {
     int32_t max_w = 0, max_h = 0;     // over the active images
 };
 
+// The cameras and neighbour lists of a call, as the C-ABI passes them.
+struct DepthCameras {
+    int32_t n_img;
+    const int32_t* wh;
+    const double *K, *R, *C;
+    const int64_t* nb_off;
+    const int32_t* nb_view;
+};
+// What sfm_depthmap works on after its checks (depth_prepare).
+struct DepthCall {
+    DepthProblem P;
+    DepthParams prm;
+    sfm_depthmap_stats st;
+};
+
+// depthmap.cpp, shared with fuse.cpp.  fn(item) for every item in [0, n), on up
+// to 16 threads.
+void depth_parallel_for(size_t n, const std::function<void(size_t)>& fn);
+// A and b of the pair (reference i, neighbour j), in double, rounded once
+void depth_pair_matrices(const DepthCameras& m, int32_t i, int32_t j, float* A, float* b);
+// The checks that the estimation, the filter and the fusion share, and the views
+// and pairs of the call.  channels / img_off / drange NULL: every image counts
+// as loaded, no ranges.
+void depth_build_problem(const char* who, const DepthCameras& m, const int32_t* channels, const int64_t* img_off,
+                         const uint8_t* pixels, const float* drange, DepthProblem& P);
+void depth_prepare(const char* who, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                   const uint8_t* pixels, const double* K, const double* R, const double* C, const int64_t* nb_off,
+                   const int32_t* nb_view, const float* drange, const float* init_depth, const float* init_normal,
+                   const sfm_depthmap_opts* opts, DepthCall& call);
+void depth_filter_prepare(const char* who, const sfm_depthmap_filter_opts* opts, DepthFilterParams& prm);
+void depth_init_maps(const DepthProblem& P, const float* init_depth, const float* init_normal, float* depth,
+                     float* normal, float* cost);
+
 #ifndef SFM_DEPTHMAP_HOST_ONLY
+// depthmap.hip.  The device buffers of a call; sfm_densify keeps them for the
+// filter and the fusion (fuse.hip).
+struct DepthResident {
+    DBuf<DepthView> views;
+    DBuf<DepthPair> pairs;
+    DBuf<uint8_t> gray;
+    DBuf<float> depth, normal, cost;
+    DBuf<unsigned long long> count;       // pixels at cost 2
+    DBuf<float> filtered;                 // the filter's depth_out
+    DBuf<uint8_t> agree;
+    DBuf<unsigned long long> fcounts;     // [2 n_img] candidates, kept
+};
+// allocates and uploads what the estimation reads (depth / normal: the initial
+// planes where init_given), enqueues its launches; n_estimated / n_invalid come
+// from depth_estimate_counts once the stream has been synchronised
+void depth_estimate_upload(hipStream_t s, const DepthProblem& P, bool init_given, const float* depth,
+                           const float* normal, DepthResident& r);
+void depth_estimate_launch(hipStream_t s, const DepthProblem& P, const DepthParams& prm, bool init_given,
+                           DepthResident& r);
+void depth_estimate_counts(const DepthProblem& P, const DepthParams& prm, unsigned long long at_worst,
+                           int64_t* n_estimated, int64_t* n_invalid);
+// the filter over r.depth / r.cost into r.filtered / r.agree / r.fcounts (allocated here; views and pairs resident)
+void depth_filter_launch(hipStream_t s, const DepthProblem& P, const DepthFilterParams& prm, DepthResident& r);
 // depthmap.hip.  Arguments already checked.  depth / normal / cost hold the
 // initial planes where init is set (cost is overwritten); seconds[3]: upload,
 // kernels, download.

@@ -156,45 +156,39 @@ struct Events {
 
 }  // namespace
 
-void depthmap_device(sfm_ctx* ctx, const DepthProblem& P, const DepthParams& prm, bool init_given, float* depth,
-                     float* normal, float* cost, int64_t* n_estimated, int64_t* n_invalid, double* seconds) {
-    CtxScope scope_(ctx);
-    hipStream_t s = ctx->stream;
+void depth_estimate_upload(hipStream_t s, const DepthProblem& P, bool init_given, const float* depth,
+                           const float* normal, DepthResident& r) {
     const size_t n_map = (size_t)P.n_map;
-    DBuf<DepthView> d_views;
-    DBuf<DepthPair> d_pairs;
-    DBuf<uint8_t> d_gray;
-    DBuf<float> d_depth, d_normal, d_cost;
-    DBuf<unsigned long long> d_count;
-    d_views.alloc(P.views.size());
-    d_pairs.alloc(std::max<size_t>(P.pairs.size(), 1));
-    d_gray.alloc(P.gray.size());
-    d_depth.alloc(n_map);
-    d_normal.alloc(3 * n_map);
-    d_cost.alloc(n_map);
-    d_count.alloc(1);
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
-    d_views.upload(P.views.data(), P.views.size(), s);
-    d_pairs.upload(P.pairs.data(), P.pairs.size(), s);
-    d_gray.upload(P.gray.data(), P.gray.size(), s);
+    r.views.alloc(P.views.size());
+    r.pairs.alloc(std::max<size_t>(P.pairs.size(), 1));
+    r.gray.alloc(P.gray.size());
+    r.depth.alloc(n_map);
+    r.normal.alloc(3 * n_map);
+    r.cost.alloc(n_map);
+    r.count.alloc(1);
+    r.views.upload(P.views.data(), P.views.size(), s);
+    r.pairs.upload(P.pairs.data(), P.pairs.size(), s);
+    r.gray.upload(P.gray.data(), P.gray.size(), s);
     if (init_given) {
-        d_depth.upload(depth, n_map, s);
-        d_normal.upload(normal, 3 * n_map, s);
+        r.depth.upload(depth, n_map, s);
+        r.normal.upload(normal, 3 * n_map, s);
     } else {
-        d_depth.zero(s);
-        d_normal.zero(s);
+        r.depth.zero(s);
+        r.normal.zero(s);
     }
-    d_cost.zero(s);
-    d_count.zero(s);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    r.cost.zero(s);
+    r.count.zero(s);
+}
+
+void depth_estimate_launch(hipStream_t s, const DepthProblem& P, const DepthParams& prm, bool init_given,
+                           DepthResident& r) {
     DepthLaunch a;
-    a.views = d_views.p;
-    a.pairs = d_pairs.p;
-    a.gray = d_gray.p;
-    a.depth = d_depth.p;
-    a.normal = d_normal.p;
-    a.cost = d_cost.p;
+    a.views = r.views.p;
+    a.pairs = r.pairs.p;
+    a.gray = r.gray.p;
+    a.depth = r.depth.p;
+    a.normal = r.normal.p;
+    a.cost = r.cost.p;
     a.prm = prm;
     a.tiles_x = (P.max_w + kDepthTileW - 1) / kDepthTileW;
     const int32_t tiles_y = (P.max_h + kDepthTileH - 1) / kDepthTileH;
@@ -212,17 +206,12 @@ void depthmap_device(sfm_ctx* ctx, const DepthProblem& P, const DepthParams& prm
                                a);
         }
     const unsigned count_blocks = (unsigned)std::min<int64_t>((P.n_map + 255) / 256, 1024);
-    hipLaunchKernelGGL(depth_count_kernel, dim3(count_blocks), dim3(256), 0, s, d_cost.p, P.n_map, d_count.p);
+    hipLaunchKernelGGL(depth_count_kernel, dim3(count_blocks), dim3(256), 0, s, r.cost.p, P.n_map, r.count.p);
     SFM_HIP(hipGetLastError());
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
-    unsigned long long at_worst = 0;
-    SFM_HIP(hipMemcpyAsync(depth, d_depth.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(normal, d_normal.p, 3 * n_map * sizeof(float), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(cost, d_cost.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(&at_worst, d_count.p, sizeof at_worst, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
-    SFM_HIP(hipStreamSynchronize(s));
-    ev.seconds(seconds);
+}
+
+void depth_estimate_counts(const DepthProblem& P, const DepthParams& prm, unsigned long long at_worst,
+                           int64_t* n_estimated, int64_t* n_invalid) {
     // the pixels outside the estimated area are at cost 2 by construction
     int64_t est = 0, border = 0;
     for (const DepthView& V : P.views) {
@@ -235,42 +224,66 @@ void depthmap_device(sfm_ctx* ctx, const DepthProblem& P, const DepthParams& prm
     *n_invalid = (int64_t)at_worst - border;
 }
 
+void depth_filter_launch(hipStream_t s, const DepthProblem& P, const DepthFilterParams& prm, DepthResident& r) {
+    const size_t n_map = (size_t)P.n_map;
+    r.filtered.alloc(n_map);
+    r.agree.alloc(n_map);
+    r.fcounts.alloc((size_t)2 * P.n_img);
+    r.fcounts.zero(s);
+    int64_t largest = 0;
+    for (const DepthView& V : P.views) largest = std::max(largest, (int64_t)V.w * V.h);
+    FilterLaunch a{r.views.p, r.pairs.p, r.depth.p, r.cost.p, r.filtered.p, r.agree.p, r.fcounts.p, prm};
+    hipLaunchKernelGGL(depth_filter_kernel, dim3((unsigned)((largest + 255) / 256), 1, (unsigned)P.n_img), dim3(256), 0, s,
+                       a);
+    SFM_HIP(hipGetLastError());
+}
+
+void depthmap_device(sfm_ctx* ctx, const DepthProblem& P, const DepthParams& prm, bool init_given, float* depth,
+                     float* normal, float* cost, int64_t* n_estimated, int64_t* n_invalid, double* seconds) {
+    CtxScope scope_(ctx);
+    hipStream_t s = ctx->stream;
+    const size_t n_map = (size_t)P.n_map;
+    DepthResident r;
+    Events ev;
+    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    depth_estimate_upload(s, P, init_given, depth, normal, r);
+    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    depth_estimate_launch(s, P, prm, init_given, r);
+    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    unsigned long long at_worst = 0;
+    SFM_HIP(hipMemcpyAsync(depth, r.depth.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipMemcpyAsync(normal, r.normal.p, 3 * n_map * sizeof(float), hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipMemcpyAsync(cost, r.cost.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipMemcpyAsync(&at_worst, r.count.p, sizeof at_worst, hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    SFM_HIP(hipStreamSynchronize(s));
+    ev.seconds(seconds);
+    depth_estimate_counts(P, prm, at_worst, n_estimated, n_invalid);
+}
+
 void depthmap_filter_device(sfm_ctx* ctx, const DepthProblem& P, const DepthFilterParams& prm, const float* depth,
                             const float* cost, float* depth_out, uint8_t* n_agree, int64_t* counts, double* seconds) {
     CtxScope scope_(ctx);
     hipStream_t s = ctx->stream;
     const size_t n_map = (size_t)P.n_map;
-    DBuf<DepthView> d_views;
-    DBuf<DepthPair> d_pairs;
-    DBuf<float> d_depth, d_cost, d_out;
-    DBuf<uint8_t> d_agree;
-    DBuf<unsigned long long> d_counts;
-    d_views.alloc(P.views.size());
-    d_pairs.alloc(std::max<size_t>(P.pairs.size(), 1));
-    d_depth.alloc(n_map);
-    d_cost.alloc(n_map);
-    d_out.alloc(n_map);
-    d_agree.alloc(n_map);
-    d_counts.alloc((size_t)2 * P.n_img);
+    DepthResident r;
+    r.views.alloc(P.views.size());
+    r.pairs.alloc(std::max<size_t>(P.pairs.size(), 1));
+    r.depth.alloc(n_map);
+    r.cost.alloc(n_map);
     Events ev;
     SFM_HIP(hipEventRecord(ev.ev[0], s));
-    d_views.upload(P.views.data(), P.views.size(), s);
-    d_pairs.upload(P.pairs.data(), P.pairs.size(), s);
-    d_depth.upload(depth, n_map, s);
-    d_cost.upload(cost, n_map, s);
-    d_counts.zero(s);
+    r.views.upload(P.views.data(), P.views.size(), s);
+    r.pairs.upload(P.pairs.data(), P.pairs.size(), s);
+    r.depth.upload(depth, n_map, s);
+    r.cost.upload(cost, n_map, s);
     SFM_HIP(hipEventRecord(ev.ev[1], s));
-    int64_t largest = 0;
-    for (const DepthView& V : P.views) largest = std::max(largest, (int64_t)V.w * V.h);
-    FilterLaunch a{d_views.p, d_pairs.p, d_depth.p, d_cost.p, d_out.p, d_agree.p, d_counts.p, prm};
-    hipLaunchKernelGGL(depth_filter_kernel, dim3((unsigned)((largest + 255) / 256), 1, (unsigned)P.n_img), dim3(256), 0, s,
-                       a);
-    SFM_HIP(hipGetLastError());
+    depth_filter_launch(s, P, prm, r);
     SFM_HIP(hipEventRecord(ev.ev[2], s));
     std::vector<unsigned long long> cnt((size_t)2 * P.n_img, 0);
-    SFM_HIP(hipMemcpyAsync(depth_out, d_out.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(n_agree, d_agree.p, n_map, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipMemcpyAsync(cnt.data(), d_counts.p, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipMemcpyAsync(depth_out, r.filtered.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipMemcpyAsync(n_agree, r.agree.p, n_map, hipMemcpyDeviceToHost, s));
+    SFM_HIP(hipMemcpyAsync(cnt.data(), r.fcounts.p, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     SFM_HIP(hipEventRecord(ev.ev[3], s));
     SFM_HIP(hipStreamSynchronize(s));
     ev.seconds(seconds);

@@ -12,8 +12,10 @@
 //                     The .mvs archive itself is not written.
 //   DepthMapEstimator the depth-map phase of DensifyPointCloud over a DenseScene and the
 //                     undistorted images: selectViews() (sfm_depth_views_select),
-//                     estimate() (sfm_depthmap), filter() (sfm_depthmap_filter), over a
-//                     backend policy with depthmap() and filter(); sfm.hpp binds it to
+//                     estimate() (sfm_depthmap), filter() (sfm_depthmap_filter), fuse()
+//                     (sfm_depthmap_fuse) into a DenseCloud, densify() (sfm_densify: the three
+//                     in one call), over a backend policy with depthmap(), filter(), fuse()
+//                     and densify(); sfm.hpp binds it to
 //                     the GPU, HostDepthMapBackend is the host twin, with the same bytes.
 // Header-only.
 #pragma once
@@ -253,14 +255,51 @@ struct HostDepthMapBackend {
         return sfm_depthmap_filter_host(n_img, wh, K, R, C, nb_off, nb_view, depth, cost, opts, depth_out, n_agree, counts,
                                         stats);
     }
+    int fuse(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+             const double* K, const double* R, const double* C, const int64_t* nb_off, const int32_t* nb_view,
+             const float* depth, const float* normal, const sfm_depthmap_fuse_opts* opts, int64_t cap_points, float* X,
+             float* N, uint8_t* rgb, uint8_t* n_views, uint32_t* view_mask, int32_t* src_image, int32_t* src_pixel,
+             sfm_depthmap_fuse_stats* stats) const {
+        return sfm_depthmap_fuse_host(n_img, wh, channels, img_off, pixels, K, R, C, nb_off, nb_view, depth, normal, opts, cap_points,
+                                      X, N, rgb, n_views, view_mask, src_image, src_pixel, stats);
+    }
+    int densify(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                const double* K, const double* R, const double* C, const int64_t* nb_off, const int32_t* nb_view,
+                const float* drange, const float* init_depth, const float* init_normal, const sfm_depthmap_opts* opts,
+                const sfm_depthmap_filter_opts* filter_opts, const sfm_depthmap_fuse_opts* fuse_opts, int64_t cap_points,
+                float* X, float* N, uint8_t* rgb, uint8_t* n_views, uint32_t* view_mask, int32_t* src_image,
+                int32_t* src_pixel, float* depth, float* normal, float* cost, float* depth_filtered, uint8_t* n_agree,
+                int64_t* counts, sfm_densify_stats* stats) const {
+        return sfm_densify_host(n_img, wh, channels, img_off, pixels, K, R, C, nb_off, nb_view, drange, init_depth, init_normal,
+                                opts, filter_opts, fuse_opts, cap_points, X, N, rgb, n_views, view_mask, src_image, src_pixel,
+                                depth, normal, cost, depth_filtered, n_agree, counts, stats);
+    }
     const char* last_error() const { return sfm_last_error(); }
+};
+
+// The product of DensifyPointCloud: one point per emitted pixel, in ascending
+// (image, y, x) order, with its normal, colour and the images that see it
+// (view_off / view_idx: sfm_dense_cloud_views' CSR, own image first).
+struct DenseCloud {
+    std::vector<float> X, N;               // [3 n]
+    std::vector<uint8_t> rgb, n_views;     // [3 n], [n]
+    std::vector<uint32_t> view_mask;
+    std::vector<int32_t> src_image, src_pixel, view_idx;
+    std::vector<int64_t> view_off;
+    size_t size() const { return src_image.size(); }
+    bool writePly(const std::string& path) const {
+        const float none[3] = {0.f, 0.f, 0.f};
+        return sfm_dense_cloud_write_ply(path.c_str(), (int64_t)size(), size() ? X.data() : none, size() ? N.data() : none,
+                                         size() ? rgb.data() : (const uint8_t*)"\0\0\0") == SFM_OK;
+    }
 };
 
 // The depth-map phase over the scene's images (scene ID order; images[k] is the
 // undistorted image of scene image k, data null where it is not loaded).
 // selectViews() fills the neighbour lists and depth ranges (or set them
-// yourself), estimate() the maps, filter() the filtered depth.  Image k's maps
-// start at pixel map_off[k].  Every step returns false when its call failed.
+// yourself), estimate() the maps, filter() the filtered depth, fuse() the cloud
+// from them; densify() does the three in one call and keeps the maps where the
+// backend computes them.  Image k's maps start at pixel map_off[k].  Every step returns false when its call failed.
 template <class Backend>
 class DepthMapEstimator {
    public:
@@ -352,6 +391,70 @@ class DepthMapEstimator {
         return true;
     }
 
+    // the cloud of the filtered maps (estimate() and filter() first)
+    bool fuse(const sfm_depthmap_fuse_opts* opts = nullptr) {
+        const size_t n = images_.size(), n_map = (size_t)map_off.back();
+        if (filtered.size() != n_map || normal.size() != 3 * n_map) return fail("fuse", "no filtered maps: filter() first", 0);
+        cameras();
+        pool();
+        std::vector<int32_t> nbv(nb_view);
+        nbv.push_back(0);
+        std::vector<float> d(filtered), nn(normal);
+        d.push_back(0.f);
+        nn.resize(nn.size() + 3, 0.f);
+        int64_t cap = 0;
+        for (size_t k = 0; k < n_map; ++k) cap += filtered[k] > 0.f;
+        reserve_cloud((size_t)cap);
+        const int rc = backend_.fuse((int32_t)n, wh_.data(), channels_.data(), img_off_.data(), pool_.data(), K_.data(),
+                                     scene_.R.data(), scene_.C.data(), nb_off.data(), nbv.data(), d.data(), nn.data(), opts,
+                                     cap, cloud.X.data(), cloud.N.data(), cloud.rgb.data(), cloud.n_views.data(),
+                                     cloud.view_mask.data(), cloud.src_image.data(), cloud.src_pixel.data(), &fuse_stats);
+        if (rc != SFM_OK) return fail("fuse", backend_.last_error(), rc);
+        return finish_cloud((size_t)fuse_stats.n_points, nbv);
+    }
+
+    // estimate(), filter() and fuse() in one call; with keep_maps the maps are fetched as those steps leave them
+    bool densify(const sfm_depthmap_opts* opts = nullptr, const sfm_depthmap_filter_opts* filter_opts = nullptr,
+                 const sfm_depthmap_fuse_opts* fuse_opts = nullptr, bool keep_maps = false) {
+        const size_t n = images_.size(), n_map = (size_t)map_off.back();
+        if (nb_off.size() != n + 1 || drange.size() < 2 * n) return fail("densify", "no neighbour lists: selectViews() first", 0);
+        cameras();
+        pool();
+        std::vector<int32_t> nbv(nb_view);
+        nbv.push_back(0);
+        reserve_cloud(n_map);
+        const size_t m = keep_maps ? n_map + 1 : 0;
+        depth.assign(m, 0.f);
+        normal.assign(3 * m, 0.f);
+        cost.assign(m, 0.f);
+        filtered.assign(m, 0.f);
+        n_agree.assign(m, 0);
+        counts.assign(keep_maps ? 2 * n + 2 : 0, 0);
+        const int rc = backend_.densify(
+            (int32_t)n, wh_.data(), channels_.data(), img_off_.data(), pool_.data(), K_.data(), scene_.R.data(),
+            scene_.C.data(), nb_off.data(), nbv.data(), drange.data(), nullptr, nullptr, opts, filter_opts, fuse_opts,
+            (int64_t)n_map, cloud.X.data(), cloud.N.data(), cloud.rgb.data(), cloud.n_views.data(), cloud.view_mask.data(),
+            cloud.src_image.data(), cloud.src_pixel.data(), keep_maps ? depth.data() : nullptr,
+            keep_maps ? normal.data() : nullptr, keep_maps ? cost.data() : nullptr, keep_maps ? filtered.data() : nullptr,
+            keep_maps ? n_agree.data() : nullptr, keep_maps ? counts.data() : nullptr, &densify_stats);
+        if (rc != SFM_OK) return fail("densify", backend_.last_error(), rc);
+        stats = densify_stats.depthmap;
+        filter_stats = densify_stats.filter;
+        fuse_stats = densify_stats.fuse;
+        if (keep_maps) {
+            depth.resize(n_map);
+            normal.resize(3 * n_map);
+            cost.resize(n_map);
+            filtered.resize(n_map);
+            n_agree.resize(n_map);
+            counts.resize(2 * n);
+        }
+        return finish_cloud((size_t)fuse_stats.n_points, nbv);
+    }
+
+    DenseCloud cloud;
+    sfm_depthmap_fuse_stats fuse_stats{};
+    sfm_densify_stats densify_stats{};
     std::vector<int64_t> map_off, nb_off, counts;
     std::vector<int32_t> nb_view;
     std::vector<double> nb_score;
@@ -374,6 +477,53 @@ class DepthMapEstimator {
         K_.resize(K_.size() + 9, 1.0);
         wh_.resize(wh_.size() + 2, 1);
     }
+    // the images as one byte pool, padded so that nothing is empty
+    void pool() {
+        channels_.clear();
+        img_off_.clear();
+        pool_.clear();
+        for (const auto& im : images_) {
+            channels_.push_back(im.channels);
+            img_off_.push_back(im.data ? (int64_t)pool_.size() : -1);
+            if (im.data && im.w > 0 && im.h > 0 && im.channels > 0)
+                pool_.insert(pool_.end(), im.data, im.data + (size_t)im.w * im.h * im.channels);
+        }
+        pool_.push_back(0);
+        channels_.push_back(1);
+        img_off_.push_back(-1);
+    }
+    void reserve_cloud(size_t cap) {
+        cloud = DenseCloud();
+        cloud.X.assign(3 * cap + 3, 0.f);
+        cloud.N.assign(3 * cap + 3, 0.f);
+        cloud.rgb.assign(3 * cap + 3, 0);
+        cloud.n_views.assign(cap + 1, 0);
+        cloud.view_mask.assign(cap + 1, 0);
+        cloud.src_image.assign(cap + 1, 0);
+        cloud.src_pixel.assign(cap + 1, 0);
+    }
+    bool finish_cloud(size_t n_points, const std::vector<int32_t>& nbv) {
+        cloud.X.resize(3 * n_points);
+        cloud.N.resize(3 * n_points);
+        cloud.rgb.resize(3 * n_points);
+        cloud.n_views.resize(n_points);
+        cloud.view_mask.resize(n_points);
+        cloud.src_image.resize(n_points);
+        cloud.src_pixel.resize(n_points);
+        const int32_t none_i = 0;
+        const uint32_t none_m = 0;
+        cloud.view_off.assign(n_points + 1, 0);
+        for (int pass = 0; pass < 2; ++pass) {
+            if (pass) cloud.view_idx.assign((size_t)cloud.view_off[n_points] + 1, 0);
+            const int rc = sfm_dense_cloud_views((int32_t)images_.size(), nb_off.data(), nbv.data(), (int64_t)n_points,
+                                                 n_points ? cloud.src_image.data() : &none_i,
+                                                 n_points ? cloud.view_mask.data() : &none_m, cloud.view_off.data(),
+                                                 pass ? cloud.view_idx.data() : nullptr);
+            if (rc != SFM_OK) return fail("fuse", sfm_last_error(), rc);
+        }
+        cloud.view_idx.resize((size_t)cloud.view_off[n_points]);
+        return true;
+    }
     static bool fail(const char* step, const char* why, int rc) {
         std::fprintf(stderr, "DepthMapEstimator::%s failed: %s (code %d)\n", step, why, rc);
         return false;
@@ -383,7 +533,9 @@ class DepthMapEstimator {
     const DenseScene& scene_;
     const std::vector<ColorImage> images_;
     std::vector<double> K_;
-    std::vector<int32_t> wh_;
+    std::vector<int32_t> wh_, channels_;
+    std::vector<int64_t> img_off_;
+    std::vector<uint8_t> pool_;
 };
 
 }  // namespace sfm

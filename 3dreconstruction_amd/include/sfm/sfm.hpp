@@ -22,7 +22,8 @@
 //                         collects (dense.hpp; sfm_dense_scene_*)
 //   DepthMapEstimator     the depth-map phase of DensifyPointCloud: view selection,
 //                         PatchMatch depth maps, the consistency filter (dense.hpp;
-//                         sfm_depth_views_select, sfm_depthmap, sfm_depthmap_filter)
+//                         sfm_depth_views_select, sfm_depthmap, sfm_depthmap_filter,
+//                         sfm_depthmap_fuse, sfm_densify; DenseCloud is its product)
 //   SIFT_Image_describer  src/nonFree/sift/SIFT_describer.hpp and detectFeature()
 //                         (sparseBuilder.cpp:575-756) on 8-bit gray buffers
 //                         (sift.hpp; sfm_sift)
@@ -274,7 +275,8 @@ inline bool UndistortImages(int32_t camera_model, const std::vector<int32_t>& im
 }
 
 // ---------------------------------------------------------------------------
-// DepthMapEstimator (dense.hpp) on the GPU: sfm_depthmap, sfm_depthmap_filter
+// DepthMapEstimator (dense.hpp) on the GPU: sfm_depthmap, sfm_depthmap_filter,
+// sfm_depthmap_fuse, sfm_densify
 // ---------------------------------------------------------------------------
 struct GpuDepthMapBackend {
     Context* ctx;
@@ -290,6 +292,25 @@ struct GpuDepthMapBackend {
                float* depth_out, uint8_t* n_agree, int64_t* counts, sfm_depthmap_filter_stats* stats) const {
         return sfm_depthmap_filter(ctx->get(), n_img, wh, K, R, C, nb_off, nb_view, depth, cost, opts, depth_out, n_agree,
                                    counts, stats);
+    }
+    int fuse(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+             const double* K, const double* R, const double* C, const int64_t* nb_off, const int32_t* nb_view,
+             const float* depth, const float* normal, const sfm_depthmap_fuse_opts* opts, int64_t cap_points, float* X,
+             float* N, uint8_t* rgb, uint8_t* n_views, uint32_t* view_mask, int32_t* src_image, int32_t* src_pixel,
+             sfm_depthmap_fuse_stats* stats) const {
+        return sfm_depthmap_fuse(ctx->get(), n_img, wh, channels, img_off, pixels, K, R, C, nb_off, nb_view, depth, normal, opts, cap_points,
+                                      X, N, rgb, n_views, view_mask, src_image, src_pixel, stats);
+    }
+    int densify(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                const double* K, const double* R, const double* C, const int64_t* nb_off, const int32_t* nb_view,
+                const float* drange, const float* init_depth, const float* init_normal, const sfm_depthmap_opts* opts,
+                const sfm_depthmap_filter_opts* filter_opts, const sfm_depthmap_fuse_opts* fuse_opts, int64_t cap_points,
+                float* X, float* N, uint8_t* rgb, uint8_t* n_views, uint32_t* view_mask, int32_t* src_image,
+                int32_t* src_pixel, float* depth, float* normal, float* cost, float* depth_filtered, uint8_t* n_agree,
+                int64_t* counts, sfm_densify_stats* stats) const {
+        return sfm_densify(ctx->get(), n_img, wh, channels, img_off, pixels, K, R, C, nb_off, nb_view, drange, init_depth, init_normal,
+                                opts, filter_opts, fuse_opts, cap_points, X, N, rgb, n_views, view_mask, src_image, src_pixel,
+                                depth, normal, cost, depth_filtered, n_agree, counts, stats);
     }
     const char* last_error() const { return sfm_last_error(); }
 };

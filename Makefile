@@ -13,7 +13,8 @@ HDRS := $(wildcard $(CSRC)/*.h) include/sfmcore.h $(wildcard $(PKG)/include/sfm/
 all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test tests/cpp/triangulate_test \
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
      tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test tests/cpp/colorize_test \
-     tests/cpp/batch_points_test tests/cpp/undistort_test tests/cpp/depthmap_test
+     tests/cpp/batch_points_test tests/cpp/undistort_test tests/cpp/depthmap_test \
+     tests/cpp/depthfuse_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -118,3 +119,14 @@ DEPTHMAP_HOST_SRCS := $(CSRC)/depthmap.cpp $(CSRC)/undistort.cpp $(CSRC)/dense_s
 tests/cpp/depthmap_test: tests/cpp/depthmap_test.cpp $(DEPTHMAP_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas $(DEPTHMAP_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY -DSFM_UNDISTORT_HOST_ONLY \
 	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(DEPTHMAP_HOST_SRCS) -lpthread
+
+# the dense fusion on the host backend: the host paths of csrc/fuse.cpp (checks,
+# pair lists, the host twin, the view lists, the PLY writer, sfm_densify_host)
+# over those of the depth maps, and the façade of include/sfm/dense.hpp compiled
+# in (no library, no HIP runtime: host only).  fuse.cpp and depthmap.cpp switch
+# contraction off themselves (#pragma at their top), as the .hip files do.
+# DEPTHFUSE_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
+DEPTHFUSE_HOST_SRCS := $(CSRC)/fuse.cpp $(DEPTHMAP_HOST_SRCS)
+tests/cpp/depthfuse_test: tests/cpp/depthfuse_test.cpp $(DEPTHFUSE_HOST_SRCS) $(HDRS)
+	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(DEPTHFUSE_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY \
+	    -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(DEPTHFUSE_HOST_SRCS) -lpthread

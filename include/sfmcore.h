@@ -1863,6 +1863,149 @@ int sfm_depthmap_filter_host(int32_t n_img, const int32_t* wh, const double* K, 
                              const sfm_depthmap_filter_opts* opts, float* depth_out, uint8_t* n_agree,
                              int64_t* counts, sfm_depthmap_filter_stats* stats);
 
+/* ------------------------------------------------------------------------ */
+/* Dense fusion                                              */
+/* The second half of DensifyPointCloud: the filtered depth maps of all      */
+/* images become one cloud of points with normals, colours and view lists.   */
+/* OpenMVS's FuseDepthMaps walks the images in order and invalidates merged  */
+/* pixels as it goes, so its result depends on that order.  This is an       */
+/* order-free restatement: a pixel's fate depends on the input maps only,    */
+/* never on what another pixel decided, so the device, the host twin and a   */
+/* restatement give the same bytes.  Nothing is pinned to OpenMVS's numbers; */
+/* this comment is the contract.                                             */
+/*                                                                          */
+/* Inputs: n_img, wh, K, R, C, nb_off, nb_view as sfm_depthmap_filter takes  */
+/* them; depth[n_map] (the filter's depth_out), normal[3 n_map]              */
+/* (sfm_depthmap's, camera frame); optionally the colour pool channels,      */
+/* img_off, pixels laid out as sfm_undistort's `out`.  pixels NULL: no       */
+/* colours (rgb is not written) and every image counts as loaded.  pixels    */
+/* given: an image with img_off < 0 counts as all-zero depth.                */
+/*                                                                          */
+/* Fusion pair list of image i (host): its own nb_view entries in order,     */
+/* then, ascending, every image j that lists i as a neighbour and is not yet */
+/* in the list; at most 32 entries, later ones are dropped and counted in    */
+/* n_pairs_dropped.  A and b of a pair (i, j) are sfm_depthmap's: in double, */
+/* rounded once.  Ki = K^-1, R and C are rounded from double once.           */
+/*                                                                          */
+/* Float arithmetic as in "Dense depth maps": single IEEE operations in the  */
+/* order written, dot(a, b) = (a0 b0 + a1 b1) + a2 b2, M [x y 1] has the     */
+/* rows (M0 x + M1 y) + M2.  For a vector v in the camera frame of image i,  */
+/* R' v has the components (R[c] v0 + R[3+c] v1) + R[6+c] v2, c = 0 1 2      */
+/* (R row-major).  World normal of a pixel: N = R' n.  World point of pixel  */
+/* p at depth d: Xw = R' (d * (Ki [p 1])) (+) C, d times each component.     */
+/* Agreement of pixel p = (x, y) of image i with depth d > 0 against pair j  */
+/* (the filter's arithmetic, against the map given): h = d * (A [p 1]) + b,  */
+/* z = h2, q = (floorf(h0 / z + 0.5f), floorf(h1 / z + 0.5f)); j agrees when */
+/* z > 0, q is inside j, depth_j(q) > 0 and |z - depth_j(q)| <= rel_tol * z  */
+/* and, when min_normal_cos > -1, dot(N_i(p), N_j(q)) >= min_normal_cos.     */
+/* Fate of a pixel with d > 0: suppressed when some agreeing pair has an     */
+/* image index j < i, otherwise emitted; a pixel with d <= 0 (or NaN) is     */
+/* neither.  The lowest agreeing index strictly descends along a chain of    */
+/* suppressed pixels, so every one of them leads to an emitted pixel.        */
+/* A fused point: the contributors are the emitted pixel itself, then its    */
+/* agreeing pairs in list order, each with its own pixel q and its own depth */
+/* depth_j(q); m of them.  X = the component sums of their world points in   */
+/* contributor order, divided by (float)m.  N = the sum of their world       */
+/* normals divided by its length sqrtf((s0 s0 + s1 s1) + s2 s2); when        */
+/* !(len > 0), the pixel's own world normal.  rgb per channel: the integer   */
+/* sum s of the contributors' bytes at their pixels (a 1-channel image       */
+/* replicated), then (2 s + m) / (2 m) in integers.  n_views = m;            */
+/* view_mask bit k: pair k of the list agrees; src_image = i;                */
+/* src_pixel = y w + x.  The cloud is in ascending (image, y, x) order of    */
+/* the emitting pixels; that order is part of the contract.                  */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_depthmap_fuse_opts {
+    float rel_tol;           /* 0.01                                           */
+    float min_normal_cos;    /* -1: the normal test is off (PatchMatch normals
+                                after three iterations are noisy; DESIGN.md
+                                §5l has the measurement)                       */
+    int64_t device_bytes;    /* budget for the resident maps, masks and colour
+                                pool; 0: the library's default, 4 GiB         */
+} sfm_depthmap_fuse_opts;
+/* [cpu] */
+void sfm_depthmap_fuse_default_options(sfm_depthmap_fuse_opts* opts);
+typedef struct sfm_depthmap_fuse_stats {
+    int64_t n_points;        /* emitted pixels: the points of the cloud        */
+    int64_t n_suppressed;
+    int64_t n_pairs_dropped; /* fusion pairs beyond 32 of an image             */
+    int64_t resident_bytes;  /* depth, normal, mask and fate of every pixel,
+                                the colour bytes, views, pairs, block tables
+                                (the cloud itself is not counted)              */
+    double seconds[3];       /* upload, kernels, download (HIP events).  Host
+                                twin: 0, the fusion's wall time, 0.            */
+} sfm_depthmap_fuse_stats;
+/* The checks are sfm_depthmap_filter's (sizes, cameras, neighbours), plus:
+ * rel_tol negative or not a number, min_normal_cos not a number or above 1,
+ * negative device_bytes, negative cap_points, null depth / normal / X, channels
+ * other than 1 or 3 on a loaded image: SFM_ERR_INVALID_ARG; the resident set
+ * exceeds device_bytes: SFM_ERR_UNSUPPORTED (the host twin refuses the same
+ * calls).  They run on the host before any device call.  X[3 cap_points];
+ * N[3 cap_points], rgb[3 cap_points], n_views, view_mask, src_image,
+ * src_pixel [cap_points] may each be NULL.  When the cloud needs more than
+ * cap_points points nothing is written, stats.n_points holds the need and the
+ * call returns SFM_ERR_INVALID_ARG with a message; the count of pixels with
+ * depth > 0 is always enough.  opts NULL = the defaults; stats may be NULL. */
+int sfm_depthmap_fuse(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                      const uint8_t* pixels, const double* K, const double* R, const double* C, const int64_t* nb_off,
+                      const int32_t* nb_view, const float* depth, const float* normal,
+                      const sfm_depthmap_fuse_opts* opts, int64_t cap_points, float* X, float* N, uint8_t* rgb,
+                      uint8_t* n_views, uint32_t* view_mask, int32_t* src_image, int32_t* src_pixel,
+                      sfm_depthmap_fuse_stats* stats);
+/* [cpu] the host twin (threads over rows): the same bytes and counts */
+int sfm_depthmap_fuse_host(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                           const uint8_t* pixels, const double* K, const double* R, const double* C,
+                           const int64_t* nb_off, const int32_t* nb_view, const float* depth, const float* normal,
+                           const sfm_depthmap_fuse_opts* opts, int64_t cap_points, float* X, float* N, uint8_t* rgb,
+                           uint8_t* n_views, uint32_t* view_mask, int32_t* src_image, int32_t* src_pixel,
+                           sfm_depthmap_fuse_stats* stats);
+/* [cpu] The view lists of a cloud as a CSR: point k sees view_idx[view_off[k]
+ * .. view_off[k + 1]): its own image first, then the images of the set bits of
+ * its view_mask in fusion-pair-list order.  view_off[n_points + 1];
+ * view_idx NULL: only view_off is filled (to size view_idx). */
+int sfm_dense_cloud_views(int32_t n_img, const int64_t* nb_off, const int32_t* nb_view, int64_t n_points,
+                          const int32_t* src_image, const uint32_t* view_mask, int64_t* view_off, int32_t* view_idx);
+/* [cpu] "ply / format binary_little_endian 1.0 / element vertex n", float
+ * x y z, then float nx ny nz when N is given, then uchar red green blue when
+ * rgb is given. */
+int sfm_dense_cloud_write_ply(const char* path, int64_t n_points, const float* X, const float* N, const uint8_t* rgb);
+
+/* Depth maps, filter and fusion in one call over one set of device buffers:
+ * the images are uploaded once and no map crosses the bus unless it is asked
+ * for.  The outputs equal, byte for byte, those of sfm_depthmap, then
+ * sfm_depthmap_filter over its depth and cost, then sfm_depthmap_fuse over the
+ * filter's depth_out and sfm_depthmap's normal with the same colour pool.  The
+ * checks are those three calls' (on the host, before any device call).  depth,
+ * normal, cost, depth_filtered, n_agree (laid out as the maps) and
+ * counts[2 n_img] are each downloaded only when non-NULL.  n_map points are
+ * always enough for cap_points. */
+typedef struct sfm_densify_stats {
+    sfm_depthmap_stats depthmap;          /* the counts; seconds are 0 on the device */
+    sfm_depthmap_filter_stats filter;     /* likewise                                */
+    sfm_depthmap_fuse_stats fuse;         /* likewise                                */
+    double seconds[3];       /* upload, everything up to the last kernel (with
+                                the one read-back of the point count),
+                                download.  Host twin: the three calls' own
+                                seconds stay in their stats; here 0, their
+                                sum, 0.                                        */
+} sfm_densify_stats;
+int sfm_densify(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                const uint8_t* pixels, const double* K, const double* R, const double* C, const int64_t* nb_off,
+                const int32_t* nb_view, const float* drange, const float* init_depth, const float* init_normal,
+                const sfm_depthmap_opts* opts, const sfm_depthmap_filter_opts* filter_opts,
+                const sfm_depthmap_fuse_opts* fuse_opts, int64_t cap_points, float* X, float* N, uint8_t* rgb,
+                uint8_t* n_views, uint32_t* view_mask, int32_t* src_image, int32_t* src_pixel, float* depth,
+                float* normal, float* cost, float* depth_filtered, uint8_t* n_agree, int64_t* counts,
+                sfm_densify_stats* stats);
+/* [cpu] the three host twins chained */
+int sfm_densify_host(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                     const uint8_t* pixels, const double* K, const double* R, const double* C, const int64_t* nb_off,
+                     const int32_t* nb_view, const float* drange, const float* init_depth, const float* init_normal,
+                     const sfm_depthmap_opts* opts, const sfm_depthmap_filter_opts* filter_opts,
+                     const sfm_depthmap_fuse_opts* fuse_opts, int64_t cap_points, float* X, float* N, uint8_t* rgb,
+                     uint8_t* n_views, uint32_t* view_mask, int32_t* src_image, int32_t* src_pixel, float* depth,
+                     float* normal, float* cost, float* depth_filtered, uint8_t* n_agree, int64_t* counts,
+                     sfm_densify_stats* stats);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -3,6 +3,10 @@ segment looking at a textured plane, 4 neighbours each, default options.
 Prints the kernel time (stats seconds[1], HIP events) and the wall time of
 calls 2-4, the host twin's wall time once (--host), and the kernel's rate in
 patch samples per second (patch samples x hypotheses x neighbours x pixels).
+Then sfm_depthmap_fuse over the filtered maps (four calls; the host twin once
+with --host, bytes compared), its kernel time against the byte bound of one
+read of depth, normal and mask plus one write of the cloud, and sfm_densify
+against the three separate calls, alternating, --rounds each.
 
     python tools/depthmap_time.py [--host] [--views 8] [--size 1024 768]
 """
@@ -51,6 +55,7 @@ def main():
     ap.add_argument("--host", action="store_true", help="also time sfm_depthmap_host once")
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--size", type=int, nargs=2, default=[1024, 768])
+    ap.add_argument("--rounds", type=int, default=3, help="rounds of densify against the three calls")
     a = ap.parse_args()
     w, h = a.size
     args = scene(a.views, w, h)
@@ -74,7 +79,39 @@ def main():
     f = api.depthmap_filter(ctx, *args[:6], dev["depth"], dev["cost"])
     out["filter"] = dict(wall_s=time.perf_counter() - t0, kernels_s=f["stats"]["seconds"][1], n_kept=f["stats"]["n_kept"],
                          n_candidates=f["stats"]["n_candidates"])
+    KEYS = ("X", "N", "rgb", "n_views", "view_mask", "src_image", "src_pixel")
+    out["fuse"] = []
+    fu = None
+    for call in range(4):
+        t0 = time.perf_counter()
+        fu = api.depthmap_fuse(ctx, *args[:6], f["depth"], dev["normal"], pool=pool)
+        wall = time.perf_counter() - t0
+        s = fu["stats"]["seconds"]
+        n_pt, n_map = fu["stats"]["n_points"], len(f["depth"])
+        # one read of depth (4), normal (12), mask and fate (5), one write of them, one write of the cloud (40 B a point)
+        bound = n_map * (4 + 12) + 2 * n_map * 5 + n_pt * 40
+        out["fuse"].append(dict(wall_s=wall, upload_s=s[0], kernels_s=s[1], download_s=s[2], bound_bytes=bound,
+                                bytes_per_s=bound / s[1] if s[1] > 0 else None))
+    out["fuse_points"], out["fuse_suppressed"] = fu["stats"]["n_points"], fu["stats"]["n_suppressed"]
+    out["densify"], out["separate"] = [], []
+    same = True
+    for rnd in range(a.rounds):
+        t0 = time.perf_counter()
+        one = api.densify(ctx, *args[:7], opts=o, pool=pool, maps=False)
+        out["densify"].append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        d3 = api.depthmap(ctx, *args[:7], opts=o, pool=pool)
+        f3 = api.depthmap_filter(ctx, *args[:6], d3["depth"], d3["cost"])
+        c3 = api.depthmap_fuse(ctx, *args[:6], f3["depth"], d3["normal"], pool=pool)
+        out["separate"].append(time.perf_counter() - t0)
+        same = same and all(one[k].tobytes() == c3[k].tobytes() for k in KEYS)
+    out["densify_equals_separate"] = same
     ctx.close()
+    if a.host:
+        t0 = time.perf_counter()
+        fh = api.depthmap_fuse(None, *args[:6], f["depth"], dev["normal"], pool=pool)
+        out["fuse_host_wall_s"] = time.perf_counter() - t0
+        out["fuse_host_equals_device"] = all(fh[k].tobytes() == fu[k].tobytes() for k in KEYS)
     if a.host:
         t0 = time.perf_counter()
         host = api.depthmap(None, *args[:7], opts=o, pool=pool)
