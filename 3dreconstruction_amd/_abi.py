@@ -357,6 +357,35 @@ class DensifyStats(C.Structure):
                 ("seconds", C.c_double * 3)]
 
 
+class MeshGrid(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_int32 * 3), ("pad", C.c_int32)]
+
+
+class TsdfOpts(C.Structure):
+    _fields_ = [("trunc", C.c_float), ("pad", C.c_int32), ("device_bytes", C.c_int64)]
+
+
+class TsdfStats(C.Structure):
+    _fields_ = [("n_observed", C.c_int64), ("resident_bytes", C.c_int64), ("seconds", C.c_double * 3)]
+
+
+class MeshOpts(C.Structure):
+    _fields_ = [("min_weight", C.c_int32), ("pad", C.c_int32)]
+
+
+class MeshStats(C.Structure):
+    _fields_ = [("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("n_degenerate", C.c_int64),
+                ("seconds", C.c_double * 3)]
+
+
+class MeshReconstructStats(C.Structure):
+    _fields_ = [("tsdf", TsdfStats), ("mesh", MeshStats), ("seconds", C.c_double * 3)]
+
+
+# the mesh stage's workgroups (csrc/mesh_point.h)
+MESH_BLOCK = 256
+MESH_TILE = (64, 4)
+
 # the fusion's limits (csrc/fuse_point.h)
 FUSE_MAX_PAIRS = 32
 FUSE_BLOCK = 256
@@ -391,6 +420,12 @@ _CLOUD = [C.c_int64, f32p, f32p, u8p, u8p, u32p, i32p, i32p]
 _DENSIFY_IN = [C.c_int32, i32p, i32p, i64p, u8p, f64p, f64p, f64p, i64p, i32p, f32p, f32p, f32p,
                C.POINTER(DepthmapOpts), C.POINTER(DepthmapFilterOpts), C.POINTER(DepthmapFuseOpts)]
 _DENSIFY_MAPS = [f32p, f32p, f32p, f32p, u8p, i64p]
+# the argument groups of the mesh entry points
+_TSDF_IN = [C.c_int32, i32p, i32p, i64p, u8p, f64p, f64p, f64p, f32p, C.POINTER(MeshGrid)]
+_MESH_OUT = [C.c_int64, C.c_int64, f32p, u8p, i32p]
+_MESH_EXTRACT = [C.POINTER(MeshGrid), f32p, u8p, u8p, u8p, C.POINTER(MeshOpts)] + _MESH_OUT + [C.POINTER(MeshStats)]
+_MESH_RECON = _TSDF_IN + [C.POINTER(TsdfOpts), C.POINTER(MeshOpts)] + _MESH_OUT + [f32p, u8p,
+                                                                                  C.POINTER(MeshReconstructStats)]
 
 SIGNATURES = [
     ("sfm_version", C.c_char_p, []),
@@ -510,6 +545,17 @@ SIGNATURES = [
     ("sfm_dense_cloud_write_ply", C.c_int, [C.c_char_p, C.c_int64, f32p, f32p, u8p]),
     ("sfm_densify", C.c_int, [C.c_void_p] + _DENSIFY_IN + _CLOUD + _DENSIFY_MAPS + [C.POINTER(DensifyStats)]),
     ("sfm_densify_host", C.c_int, _DENSIFY_IN + _CLOUD + _DENSIFY_MAPS + [C.POINTER(DensifyStats)]),
+    ("sfm_mesh_grid_fit", C.c_int, [C.c_int64, f32p, C.c_int32, C.c_int32, C.POINTER(MeshGrid)]),
+    ("sfm_tsdf_default_options", None, [C.POINTER(TsdfOpts)]),
+    ("sfm_mesh_default_options", None, [C.POINTER(MeshOpts)]),
+    ("sfm_tsdf_integrate", C.c_int, [C.c_void_p] + _TSDF_IN + [C.POINTER(TsdfOpts), f32p, u8p, u8p, u8p,
+                                                                C.POINTER(TsdfStats)]),
+    ("sfm_tsdf_integrate_host", C.c_int, _TSDF_IN + [C.POINTER(TsdfOpts), f32p, u8p, u8p, u8p, C.POINTER(TsdfStats)]),
+    ("sfm_mesh_extract", C.c_int, [C.c_void_p] + _MESH_EXTRACT),
+    ("sfm_mesh_extract_host", C.c_int, _MESH_EXTRACT),
+    ("sfm_mesh_reconstruct", C.c_int, [C.c_void_p] + _MESH_RECON),
+    ("sfm_mesh_reconstruct_host", C.c_int, _MESH_RECON),
+    ("sfm_mesh_write_ply", C.c_int, [C.c_char_p, C.c_int64, f32p, u8p, C.c_int64, i32p]),
     ("sfm_sift_options_default", None, [C.POINTER(SiftOptions)]),
     ("sfm_sift", C.c_int, [C.c_void_p, u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
                            f32p, u8p, i64p, C.POINTER(SiftSummary)]),

@@ -1738,3 +1738,180 @@ def dense_cloud_write_ply(path, X, N=None, rgb=None):
     _check(abi.load().sfm_dense_cloud_write_ply(_b(path), n, abi.ptr(X if n else np.zeros(3, np.float32), abi.f32p),
                                                abi.ptr(pad(N, np.float32), abi.f32p), abi.ptr(pad(rgb, np.uint8), abi.u8p)),
            "sfm_dense_cloud_write_ply")
+
+
+# ---- mesh -----------------------------------------------------------------------------
+def tsdf_default_options():
+    o = abi.TsdfOpts()
+    abi.load().sfm_tsdf_default_options(C.byref(o))
+    return o
+
+
+def mesh_default_options():
+    o = abi.MeshOpts()
+    abi.load().sfm_mesh_default_options(C.byref(o))
+    return o
+
+
+def mesh_grid(origin, voxel, dims):
+    """an sfm_mesh_grid from origin [3], voxel and dims (nx, ny, nz)"""
+    g = abi.MeshGrid()
+    g.origin[:] = [float(v) for v in origin]
+    g.voxel = float(voxel)
+    g.dims[:] = [int(v) for v in dims]
+    return g
+
+
+def mesh_grid_fit(X, resolution, margin_voxels=2):
+    """sfm_mesh_grid_fit: the grid (abi.MeshGrid) around the cloud X [n, 3]"""
+    X = np.ascontiguousarray(np.asarray(X, np.float32).reshape(-1))
+    g = abi.MeshGrid()
+    _check(abi.load().sfm_mesh_grid_fit(len(X) // 3, abi.ptr(X if len(X) else np.zeros(3, np.float32), abi.f32p),
+                                        int(resolution), int(margin_voxels), C.byref(g)), "sfm_mesh_grid_fit")
+    return g
+
+
+def _tsdf_inputs(wh, K, R, Cc, depth, images, pool):
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    n_img = len(wh) // 2
+    K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(-1))
+    R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1))
+    Cc = np.ascontiguousarray(np.asarray(Cc, np.float64).reshape(-1))
+    assert len(K) == 9 * n_img and len(R) == 9 * n_img and len(Cc) == 3 * n_img
+    n_map = int((wh[0::2].astype(np.int64) * wh[1::2]).sum()) if n_img and (wh > 0).all() else 0
+    depth = np.ascontiguousarray(np.asarray(depth, np.float32).reshape(-1))
+    assert n_map == 0 or len(depth) == n_map
+    colours = images is not None or pool is not None
+    channels, img_off, pixels = (pool if pool is not None else _pixel_pool(images)) if colours else (None, None, None)
+    one = np.zeros(9)
+    keep = (wh, K, R, Cc, depth, channels, img_off, pixels, one)
+    args = (n_img, abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p), abi.ptr(channels, abi.i32p),
+            abi.ptr(img_off, abi.i64p), abi.ptr(pixels, abi.u8p), abi.ptr(K if n_img else one, abi.f64p),
+            abi.ptr(R if n_img else one, abi.f64p), abi.ptr(Cc if n_img else one, abi.f64p),
+            abi.ptr(depth if n_map else np.zeros(1, np.float32), abi.f32p))
+    return args, colours, keep
+
+
+def _grid_points(grid):
+    d = [int(v) for v in grid.dims]
+    return d[0] * d[1] * d[2] if min(d) > 0 and d[0] * d[1] * d[2] < 2 ** 31 else 0
+
+
+def tsdf_integrate(ctx, wh, K, R, Cc, depth, grid, images=None, opts=None, pool=None):
+    """sfm_tsdf_integrate (ctx None: sfm_tsdf_integrate_host) over the filter's
+    depth (flat); images as in undistort(), None: no colours.  dict(tsdf
+    (float32), weight (uint8), rgb [n, 3] and has_rgb (uint8) or None, flat over
+    the lattice's raster; stats)."""
+    lib = abi.load()
+    args, colours, keep = _tsdf_inputs(wh, K, R, Cc, depth, images, pool)
+    n = max(_grid_points(grid), 1)
+    tsdf, weight = np.zeros(n, np.float32), np.zeros(n, np.uint8)
+    rgb, has = (np.zeros(3 * n, np.uint8), np.zeros(n, np.uint8)) if colours else (None, None)
+    st = abi.TsdfStats()
+    args = args + (C.byref(grid), C.byref(opts) if opts is not None else None, abi.ptr(tsdf, abi.f32p),
+                   abi.ptr(weight, abi.u8p), abi.ptr(rgb, abi.u8p), abi.ptr(has, abi.u8p), C.byref(st))
+    if ctx is None:
+        _check(lib.sfm_tsdf_integrate_host(*args), "sfm_tsdf_integrate_host")
+    else:
+        _check(lib.sfm_tsdf_integrate(ctx.h, *args), "sfm_tsdf_integrate")
+    return dict(tsdf=tsdf, weight=weight, rgb=rgb.reshape(-1, 3) if colours else None, has_rgb=has,
+                stats=_struct_dict(st))
+
+
+def _mesh_arrays(cap_v, cap_t, fill=0):
+    return dict(V=np.full(3 * max(cap_v, 1), fill, np.float32), rgb=np.full(3 * max(cap_v, 1), fill, np.uint8),
+                tri=np.full(3 * max(cap_t, 1), fill, np.int32))
+
+
+def _mesh_ptrs(cap_v, cap_t, a):
+    return (cap_v, cap_t, abi.ptr(a["V"], abi.f32p), abi.ptr(a["rgb"], abi.u8p), abi.ptr(a["tri"], abi.i32p))
+
+
+def _mesh_dict(a, st, colours, stats):
+    nv, nt = st["n_vertices"], st["n_triangles"]
+    return dict(V=a["V"][:3 * nv].reshape(-1, 3), rgb=a["rgb"][:3 * nv].reshape(-1, 3) if colours else None,
+                tri=a["tri"][:3 * nt].reshape(-1, 3), stats=stats)
+
+
+def mesh_extract_raw(ctx, grid, tsdf, weight, rgb=None, has_rgb=None, opts=None, cap_vertices=0, cap_triangles=0,
+                     fill=0):
+    """sfm_mesh_extract (ctx None: sfm_mesh_extract_host) without the check of
+    its return code: (rc, the mesh's arrays at their full capacity, pre-filled
+    with `fill`, the stats dict)."""
+    lib = abi.load()
+    tsdf = np.ascontiguousarray(np.asarray(tsdf, np.float32).reshape(-1))
+    weight = np.ascontiguousarray(np.asarray(weight, np.uint8).reshape(-1))
+    n = _grid_points(grid)
+    assert n == 0 or (len(tsdf) == n and len(weight) == n)
+    if rgb is not None:
+        rgb = np.ascontiguousarray(np.asarray(rgb, np.uint8).reshape(-1))
+        has_rgb = np.ascontiguousarray(np.asarray(has_rgb, np.uint8).reshape(-1))
+        assert n == 0 or (len(rgb) == 3 * n and len(has_rgb) == n)
+    arrays = _mesh_arrays(int(cap_vertices), int(cap_triangles), fill)
+    st = abi.MeshStats()
+    args = (C.byref(grid), abi.ptr(tsdf, abi.f32p), abi.ptr(weight, abi.u8p), abi.ptr(rgb, abi.u8p),
+            abi.ptr(has_rgb if rgb is not None else None, abi.u8p), C.byref(opts) if opts is not None else None
+            ) + _mesh_ptrs(int(cap_vertices), int(cap_triangles), arrays) + (C.byref(st),)
+    rc = lib.sfm_mesh_extract_host(*args) if ctx is None else lib.sfm_mesh_extract(ctx.h, *args)
+    return rc, arrays, _struct_dict(st)
+
+
+def mesh_extract(ctx, grid, tsdf, weight, rgb=None, has_rgb=None, opts=None, cap_vertices=None, cap_triangles=None):
+    """sfm_mesh_extract (ctx None: sfm_mesh_extract_host).  Without caps the
+    call is made twice: once to learn the needs, once with them.  dict(V [n, 3]
+    float32, rgb [n, 3] uint8 or None, tri [m, 3] int32, stats)."""
+    where = "sfm_mesh_extract_host" if ctx is None else "sfm_mesh_extract"
+    cv, ct = (0, 0) if cap_vertices is None else (cap_vertices, cap_triangles)
+    rc, arrays, st = mesh_extract_raw(ctx, grid, tsdf, weight, rgb, has_rgb, opts, cv, ct)
+    if cap_vertices is None and rc == abi.SFM_ERR_INVALID_ARG and st["n_vertices"] > 0:
+        rc, arrays, st = mesh_extract_raw(ctx, grid, tsdf, weight, rgb, has_rgb, opts, st["n_vertices"], st["n_triangles"])
+    _check(rc, where)
+    return _mesh_dict(arrays, st, rgb is not None, st)
+
+
+def mesh_reconstruct_raw(ctx, wh, K, R, Cc, depth, grid, images=None, tsdf_opts=None, mesh_opts=None, pool=None,
+                         cap_vertices=0, cap_triangles=0, volume=False, fill=0):
+    """sfm_mesh_reconstruct (ctx None: sfm_mesh_reconstruct_host) without the
+    check of its return code: (rc, arrays, stats dict, tsdf, weight); the volume
+    is fetched only with volume=True."""
+    lib = abi.load()
+    args, colours, keep = _tsdf_inputs(wh, K, R, Cc, depth, images, pool)
+    n = max(_grid_points(grid), 1)
+    tsdf, weight = (np.zeros(n, np.float32), np.zeros(n, np.uint8)) if volume else (None, None)
+    arrays = _mesh_arrays(int(cap_vertices), int(cap_triangles), fill)
+    st = abi.MeshReconstructStats()
+    opt = lambda o: C.byref(o) if o is not None else None
+    args = args + (C.byref(grid), opt(tsdf_opts), opt(mesh_opts)) + _mesh_ptrs(int(cap_vertices), int(cap_triangles), arrays) + (
+        abi.ptr(tsdf, abi.f32p), abi.ptr(weight, abi.u8p), C.byref(st))
+    rc = lib.sfm_mesh_reconstruct_host(*args) if ctx is None else lib.sfm_mesh_reconstruct(ctx.h, *args)
+    return rc, arrays, _struct_dict(st), tsdf, weight
+
+
+def mesh_reconstruct(ctx, wh, K, R, Cc, depth, grid, images=None, tsdf_opts=None, mesh_opts=None, pool=None,
+                     cap_vertices=None, cap_triangles=None, volume=False):
+    """sfm_mesh_reconstruct (ctx None: sfm_mesh_reconstruct_host): integration
+    and extraction in one call.  The mesh as mesh_extract() returns it, plus,
+    with volume=True, tsdf and weight.  Without caps the call is made twice."""
+    where = "sfm_mesh_reconstruct_host" if ctx is None else "sfm_mesh_reconstruct"
+    call = lambda cv, ct: mesh_reconstruct_raw(ctx, wh, K, R, Cc, depth, grid, images, tsdf_opts, mesh_opts, pool, cv, ct,
+                                               volume)
+    rc, arrays, st, tsdf, weight = call(*((0, 0) if cap_vertices is None else (cap_vertices, cap_triangles)))
+    if cap_vertices is None and rc == abi.SFM_ERR_INVALID_ARG and st["mesh"]["n_vertices"] > 0:
+        rc, arrays, st, tsdf, weight = call(st["mesh"]["n_vertices"], st["mesh"]["n_triangles"])
+    _check(rc, where)
+    out = _mesh_dict(arrays, st["mesh"], images is not None or pool is not None, st)
+    if volume:
+        out.update(tsdf=tsdf, weight=weight)
+    return out
+
+
+def mesh_write_ply(path, V, tri, rgb=None):
+    """sfm_mesh_write_ply: binary little-endian x y z [red green blue], then the faces"""
+    V = np.ascontiguousarray(np.asarray(V, np.float32).reshape(-1, 3))
+    tri = np.ascontiguousarray(np.asarray(tri, np.int32).reshape(-1, 3))
+    rgb = None if rgb is None else np.ascontiguousarray(np.asarray(rgb, np.uint8).reshape(-1, 3))
+    assert rgb is None or len(rgb) == len(V)
+    n, m = len(V), len(tri)
+    _check(abi.load().sfm_mesh_write_ply(_b(path), n, abi.ptr(V if n else np.zeros(3, np.float32), abi.f32p),
+                                        abi.ptr(rgb if rgb is None or n else np.zeros(3, np.uint8), abi.u8p), m,
+                                        abi.ptr(tri if m else np.zeros(3, np.int32), abi.i32p)), "sfm_mesh_write_ply")

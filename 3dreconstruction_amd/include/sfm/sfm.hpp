@@ -24,6 +24,9 @@
 //                         PatchMatch depth maps, the consistency filter (dense.hpp;
 //                         sfm_depth_views_select, sfm_depthmap, sfm_depthmap_filter,
 //                         sfm_depthmap_fuse, sfm_densify; DenseCloud is its product)
+//   MeshReconstructor     the first step of meshWork(): the filtered depth maps into a
+//                         TSDF volume and its zero level set as a Mesh (mesh.hpp;
+//                         sfm_tsdf_integrate, sfm_mesh_extract, sfm_mesh_reconstruct)
 //   SIFT_Image_describer  src/nonFree/sift/SIFT_describer.hpp and detectFeature()
 //                         (sparseBuilder.cpp:575-756) on 8-bit gray buffers
 //                         (sift.hpp; sfm_sift)
@@ -57,6 +60,7 @@
 #include "dense.hpp"
 #include "frames.hpp"
 #include "localizer.hpp"
+#include "mesh.hpp"
 #include "reconstruction.hpp"
 #include "relative_pose.hpp"
 #include "sift.hpp"
@@ -315,6 +319,37 @@ struct GpuDepthMapBackend {
     const char* last_error() const { return sfm_last_error(); }
 };
 using GpuDepthMapEstimator = DepthMapEstimator<GpuDepthMapBackend>;
+
+// ---------------------------------------------------------------------------
+// MeshReconstructor (mesh.hpp) on the GPU: sfm_tsdf_integrate, sfm_mesh_extract,
+// sfm_mesh_reconstruct
+// ---------------------------------------------------------------------------
+struct GpuMeshBackend {
+    Context* ctx;
+    int integrate(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                  const double* K, const double* R, const double* C, const float* depth, const sfm_mesh_grid* grid,
+                  const sfm_tsdf_opts* opts, float* tsdf, uint8_t* weight, uint8_t* rgb, uint8_t* has_rgb,
+                  sfm_tsdf_stats* stats) const {
+        return sfm_tsdf_integrate(ctx->get(), n_img, wh, channels, img_off, pixels, K, R, C, depth, grid, opts, tsdf, weight,
+                                  rgb, has_rgb, stats);
+    }
+    int extract(const sfm_mesh_grid* grid, const float* tsdf, const uint8_t* weight, const uint8_t* rgb,
+                const uint8_t* has_rgb, const sfm_mesh_opts* opts, int64_t cap_vertices, int64_t cap_triangles, float* V,
+                uint8_t* vertex_rgb, int32_t* tri, sfm_mesh_stats* stats) const {
+        return sfm_mesh_extract(ctx->get(), grid, tsdf, weight, rgb, has_rgb, opts, cap_vertices, cap_triangles, V,
+                                vertex_rgb, tri, stats);
+    }
+    int reconstruct(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                    const uint8_t* pixels, const double* K, const double* R, const double* C, const float* depth,
+                    const sfm_mesh_grid* grid, const sfm_tsdf_opts* tsdf_opts, const sfm_mesh_opts* mesh_opts,
+                    int64_t cap_vertices, int64_t cap_triangles, float* V, uint8_t* vertex_rgb, int32_t* tri, float* tsdf,
+                    uint8_t* weight, sfm_mesh_reconstruct_stats* stats) const {
+        return sfm_mesh_reconstruct(ctx->get(), n_img, wh, channels, img_off, pixels, K, R, C, depth, grid, tsdf_opts,
+                                    mesh_opts, cap_vertices, cap_triangles, V, vertex_rgb, tri, tsdf, weight, stats);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+using GpuMeshReconstructor = MeshReconstructor<GpuMeshBackend>;
 
 // ---------------------------------------------------------------------------
 // SIFT_Image_describer (sift.hpp) on the GPU: sfm_sift

@@ -14,7 +14,7 @@ all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test t
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
      tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test tests/cpp/colorize_test \
      tests/cpp/batch_points_test tests/cpp/undistort_test tests/cpp/depthmap_test \
-     tests/cpp/depthfuse_test
+     tests/cpp/depthfuse_test tests/cpp/mesh_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -130,3 +130,14 @@ DEPTHFUSE_HOST_SRCS := $(CSRC)/fuse.cpp $(DEPTHMAP_HOST_SRCS)
 tests/cpp/depthfuse_test: tests/cpp/depthfuse_test.cpp $(DEPTHFUSE_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(DEPTHFUSE_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY \
 	    -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(DEPTHFUSE_HOST_SRCS) -lpthread
+
+# the mesh stage on the host backend: the host paths of csrc/mesh.cpp (checks,
+# the grid fit, the host twins of the integration and the extraction, the PLY
+# writer) over those of the depth maps (its thread pool), and the façade of
+# include/sfm/mesh.hpp compiled in (no library, no HIP runtime: host only).
+# mesh.cpp switches contraction off itself (#pragma at its top), as mesh.hip does.
+# MESH_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
+MESH_HOST_SRCS := $(CSRC)/mesh.cpp $(DEPTHMAP_HOST_SRCS)
+tests/cpp/mesh_test: tests/cpp/mesh_test.cpp $(MESH_HOST_SRCS) $(HDRS)
+	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(MESH_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY \
+	    -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(MESH_HOST_SRCS) -lpthread

@@ -2006,6 +2006,184 @@ int sfm_densify_host(int32_t n_img, const int32_t* wh, const int32_t* channels, 
                      float* normal, float* cost, float* depth_filtered, uint8_t* n_agree, int64_t* counts,
                      sfm_densify_stats* stats);
 
+/* ------------------------------------------------------------------------ */
+/* Mesh                                                      */
+/* The first step of meshWork(): a surface from the filtered depth maps.     */
+/* OpenMVS's ReconstructMesh is a Delaunay tetrahedralisation with a graph   */
+/* cut: serial and order dependent.  This is a method without an order: the  */
+/* depth maps are integrated into a truncated signed distance volume (TSDF), */
+/* one lattice point at a time, and the zero level set is extracted by       */
+/* marching tetrahedra over the Kuhn split of every cell, with the vertices  */
+/* and triangles placed by prefix sums.  The device, the host twin and a     */
+/* restatement give the same bytes.  Nothing is pinned to OpenMVS's numbers; */
+/* this comment is the contract.                                             */
+/*                                                                          */
+/* Float arithmetic as in "Dense depth maps": single IEEE operations in the  */
+/* order written, dot(a, b) = (a0 b0 + a1 b1) + a2 b2, M q has the rows      */
+/* dot(M_row, q).                                                            */
+/*                                                                          */
+/* Grid: origin[3], voxel > 0, dims = (nx, ny, nz), each >= 1.  Lattice      */
+/* point (i, j, k) has the raster index (k ny + j) nx + i and the position   */
+/* origin_c + (float)i_c * voxel per component.  nx ny nz >= 2^31, ny above  */
+/* 262140 or nz above 65535: SFM_ERR_UNSUPPORTED.                            */
+/*                                                                          */
+/* Integration.  Inputs n_img, wh, channels, img_off, pixels, K, R, C and    */
+/* depth[n_map] as sfm_depthmap_fuse takes them (no neighbour lists, no      */
+/* normals): pixels NULL: no colours, every image has a depth map; pixels    */
+/* given: an image with img_off < 0 has none.  Per image the host works out  */
+/* M = K R in double and rounds once; C is rounded once.  trunc is the       */
+/* option, or 3.0f * voxel (in float) when it is 0.  A lattice point X takes */
+/* the images that have a depth map in ascending index order:                */
+/*   q = X - C, h = M q, z = h2; skip the image unless z > 0;                */
+/*   x = floorf(h0 / z + 0.5f), y = floorf(h1 / z + 0.5f); skip unless       */
+/*   0 <= x <= w - 1 and 0 <= y <= h - 1;  d = depth(x, y); skip unless      */
+/*   d > 0;  sd = d - z; skip when sd < -trunc;                              */
+/*   t = (sd < trunc ? sd : trunc) / trunc;  sum = sum + t;  count += 1;     */
+/*   with colours, when fabsf(sd) <= trunc: the pixel's bytes are added to   */
+/*   three integer sums s (a 1-channel image replicated) and m += 1.         */
+/* tsdf = sum / (float)count, or 0 when count is 0; weight = min(count,      */
+/* 255); rgb = (2 s + m) / (2 m) per channel in integers, 0 0 0 when m is 0; */
+/* has_rgb = (m > 0).  Limit: the depth is sampled at the nearest pixel, as  */
+/* the filter and the fusion do; there is no bilinear sampling.              */
+/*                                                                          */
+/* Extraction.  A lattice point is observed when weight >= min_weight; an    */
+/* observed point is inside when tsdf < 0.  Cell (i, j, k) (i < nx - 1, ..)  */
+/* is live when its 8 corners are observed.  A lattice point owns the 7      */
+/* edges to + (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), slots */
+/* 0 to 6.  An owned edge carries a vertex when both ends are observed,      */
+/* exactly one end is inside and at least one live cell has both ends among  */
+/* its corners; so no vertex is unreferenced.  Vertices come in ascending    */
+/* (raster index of the owner, slot) order.  The vertex of edge a -> b       */
+/* (owner a): u = ta / (ta - tb), then Xa + u * (Xb - Xa) per component.     */
+/* Its colour is a's when u < 0.5f, else b's; when that end has no colour    */
+/* (has_rgb 0), the other end's; when neither has, 0 0 0.                    */
+/* Live cells are taken in raster order, each split into six tetrahedra      */
+/* along the axis permutations xyz, xzy, yxz, yzx, zxy, zyx: permutation     */
+/* (p1, p2, p3) gives the corners c0 = (0,0,0), c1 = e_p1, c2 = c1 + e_p2,   */
+/* c3 = (1,1,1).  v(n m) is the vertex on the edge between corners n and m.  */
+/* By the number of inside corners: 0 or 4: nothing.  One corner a differs   */
+/* from the other three b < c < d (corner order): the triangle (v(a b),      */
+/* v(a c), v(a d)).  Two inside a1 < a2 and two outside b1 < b2: q0 =        */
+/* v(a1 b1), q1 = v(a1 b2), q2 = v(a2 b2), q3 = v(a2 b1) and the triangles   */
+/* (q0, q1, q2), (q0, q2, q3).  The second and third vertex of a triangle    */
+/* (A, B, C) are swapped when needed so that, with every crossing put at its */
+/* edge's midpoint, (B - A) x (C - A) has a positive dot product with (mean  */
+/* of the outside corners - mean of the inside corners); that product is a   */
+/* non-zero multiple of the tetrahedron's volume in every case, so the rule  */
+/* fixes a 6 x 16 table.  Triangles are int32 vertex indices in (cell        */
+/* raster, tetrahedron, triangle) order; that order and the vertices' are    */
+/* part of the contract.  More than 2^31 - 1 vertices: SFM_ERR_UNSUPPORTED.  */
+/* Limit: a sample with tsdf == 0 counts as outside, so the edges that end   */
+/* in it give vertices that coincide (up to rounding) and triangles without  */
+/* area; n_degenerate counts the triangles of which two vertices lie on      */
+/* edges that end in the same corner with tsdf == 0.                         */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_mesh_grid {
+    float origin[3];
+    float voxel;
+    int32_t dims[3];         /* nx ny nz                                       */
+    int32_t pad;
+} sfm_mesh_grid;
+/* [cpu] The grid around a cloud, in double: lo / hi = the bounding box of
+ * X[3 n_points], voxel_d = (the longest side) / resolution, voxel =
+ * (float)voxel_d, origin_c = (float)(lo_c - margin_voxels * voxel_d), dims_c =
+ * floor((hi_c - lo_c) / voxel_d) + 2 + 2 margin_voxels.  n_points < 1,
+ * resolution < 1, margin_voxels < 0, a coordinate that is not finite or a
+ * cloud without extent: SFM_ERR_INVALID_ARG; the grid's limits above:
+ * SFM_ERR_UNSUPPORTED. */
+int sfm_mesh_grid_fit(int64_t n_points, const float* X, int32_t resolution, int32_t margin_voxels, sfm_mesh_grid* grid);
+
+typedef struct sfm_tsdf_opts {
+    float trunc;             /* world units; 0: 3 * voxel                      */
+    int32_t pad;
+    int64_t device_bytes;    /* budget for the resident maps, colours and
+                                volume; 0: the library's default, 4 GiB       */
+} sfm_tsdf_opts;
+/* [cpu] */
+void sfm_tsdf_default_options(sfm_tsdf_opts* opts);
+typedef struct sfm_tsdf_stats {
+    int64_t n_observed;      /* lattice points with weight > 0                 */
+    int64_t resident_bytes;  /* the depth maps, the colour bytes, the views, 9
+                                bytes a lattice point and the block counts     */
+    double seconds[3];       /* upload, kernels, download (HIP events).  Host
+                                twin: 0, the wall time, 0.                     */
+} sfm_tsdf_stats;
+/* tsdf[n], weight[n], rgb[3 n], has_rgb[n] over the n = nx ny nz lattice
+ * points in raster order; rgb and has_rgb are written only when pixels is
+ * given and may be NULL otherwise.  Checks (on the host, before any device
+ * call; the host twin refuses the same calls): negative n_img, a null
+ * argument, a non-positive image size, a camera that is not finite, channels
+ * other than 1 or 3 on an image with colours, a voxel that is not positive and
+ * finite, an origin that is not finite, a dimension below 1, trunc negative or
+ * not a number, negative device_bytes: SFM_ERR_INVALID_ARG; the grid's limits,
+ * an image of 2^31 pixels or more, a resident set beyond device_bytes:
+ * SFM_ERR_UNSUPPORTED.  opts NULL = the defaults; stats may be NULL. */
+int sfm_tsdf_integrate(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                       const uint8_t* pixels, const double* K, const double* R, const double* C, const float* depth,
+                       const sfm_mesh_grid* grid, const sfm_tsdf_opts* opts, float* tsdf, uint8_t* weight, uint8_t* rgb,
+                       uint8_t* has_rgb, sfm_tsdf_stats* stats);
+/* [cpu] the host twin (threads over rows): the same bytes and counts */
+int sfm_tsdf_integrate_host(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                            const uint8_t* pixels, const double* K, const double* R, const double* C, const float* depth,
+                            const sfm_mesh_grid* grid, const sfm_tsdf_opts* opts, float* tsdf, uint8_t* weight,
+                            uint8_t* rgb, uint8_t* has_rgb, sfm_tsdf_stats* stats);
+
+typedef struct sfm_mesh_opts {
+    int32_t min_weight;      /* 1 .. 255; default 1                            */
+    int32_t pad;
+} sfm_mesh_opts;
+/* [cpu] */
+void sfm_mesh_default_options(sfm_mesh_opts* opts);
+typedef struct sfm_mesh_stats {
+    int64_t n_vertices;
+    int64_t n_triangles;
+    int64_t n_degenerate;    /* see the limit above                            */
+    double seconds[3];       /* upload, kernels (with the one read-back of the
+                                totals), download.  Host twin: 0, wall, 0.     */
+} sfm_mesh_stats;
+/* V[3 cap_vertices], rgb[3 cap_vertices] (written when the volume's rgb and
+ * has_rgb are given; may be NULL), tri[3 cap_triangles].  The caps behave as
+ * cap_points does in the fusion: when either is too small nothing is written,
+ * stats holds both needs and the call returns SFM_ERR_INVALID_ARG with a
+ * message.  Checks: the grid's, a null tsdf / weight, rgb without has_rgb,
+ * min_weight outside 1 .. 255, a negative cap, a null V or tri with a positive
+ * cap: SFM_ERR_INVALID_ARG. */
+int sfm_mesh_extract(sfm_ctx* ctx, const sfm_mesh_grid* grid, const float* tsdf, const uint8_t* weight,
+                     const uint8_t* rgb, const uint8_t* has_rgb, const sfm_mesh_opts* opts, int64_t cap_vertices,
+                     int64_t cap_triangles, float* V, uint8_t* vertex_rgb, int32_t* tri, sfm_mesh_stats* stats);
+/* [cpu] the host twin: the same bytes and counts */
+int sfm_mesh_extract_host(const sfm_mesh_grid* grid, const float* tsdf, const uint8_t* weight, const uint8_t* rgb,
+                          const uint8_t* has_rgb, const sfm_mesh_opts* opts, int64_t cap_vertices, int64_t cap_triangles,
+                          float* V, uint8_t* vertex_rgb, int32_t* tri, sfm_mesh_stats* stats);
+
+/* Integration and extraction in one call; the volume stays on the device and
+ * tsdf[n] / weight[n] are downloaded only when non-NULL.  The outputs equal,
+ * byte for byte, those of sfm_tsdf_integrate, then sfm_mesh_extract over its
+ * volume.  The checks are the two calls'. */
+typedef struct sfm_mesh_reconstruct_stats {
+    sfm_tsdf_stats tsdf;     /* the counts; seconds are 0 on the device        */
+    sfm_mesh_stats mesh;     /* likewise                                       */
+    double seconds[3];       /* upload, everything up to the last kernel,
+                                download.  Host twin: 0, the two calls' sum, 0 */
+} sfm_mesh_reconstruct_stats;
+int sfm_mesh_reconstruct(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                         const uint8_t* pixels, const double* K, const double* R, const double* C, const float* depth,
+                         const sfm_mesh_grid* grid, const sfm_tsdf_opts* tsdf_opts, const sfm_mesh_opts* mesh_opts,
+                         int64_t cap_vertices, int64_t cap_triangles, float* V, uint8_t* vertex_rgb, int32_t* tri,
+                         float* tsdf, uint8_t* weight, sfm_mesh_reconstruct_stats* stats);
+/* [cpu] the two host twins chained */
+int sfm_mesh_reconstruct_host(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                              const uint8_t* pixels, const double* K, const double* R, const double* C,
+                              const float* depth, const sfm_mesh_grid* grid, const sfm_tsdf_opts* tsdf_opts,
+                              const sfm_mesh_opts* mesh_opts, int64_t cap_vertices, int64_t cap_triangles, float* V,
+                              uint8_t* vertex_rgb, int32_t* tri, float* tsdf, uint8_t* weight,
+                              sfm_mesh_reconstruct_stats* stats);
+/* [cpu] "ply / format binary_little_endian 1.0 / element vertex n", float
+ * x y z, then uchar red green blue when rgb is given, then "element face m /
+ * property list uchar int vertex_indices": a byte 3 and three int32 a face. */
+int sfm_mesh_write_ply(const char* path, int64_t n_vertices, const float* V, const uint8_t* rgb, int64_t n_triangles,
+                       const int32_t* tri);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
