@@ -386,6 +386,36 @@ class MeshReconstructStats(C.Structure):
 MESH_BLOCK = 256
 MESH_TILE = (64, 4)
 
+
+class MeshTextureOpts(C.Structure):
+    _fields_ = [("cell", C.c_int32), ("fill", C.c_uint8 * 3), ("pad", C.c_uint8), ("device_bytes", C.c_int64)]
+
+
+class MeshFaceViewsStats(C.Structure):
+    _fields_ = [("n_textured", C.c_int64), ("n_untextured", C.c_int64), ("n_not_drawable", C.c_int64),
+                ("sum_pixels", C.c_int64), ("resident_bytes", C.c_int64), ("seconds", C.c_double * 3)]
+
+
+class MeshBakeStats(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("cols", C.c_int32), ("pad", C.c_int32),
+                ("resident_bytes", C.c_int64), ("seconds", C.c_double * 3)]
+
+
+class MeshTextureStats(C.Structure):
+    _fields_ = [("views", MeshFaceViewsStats), ("bake", MeshBakeStats), ("resident_bytes", C.c_int64),
+                ("seconds", C.c_double * 3)]
+
+
+# the texturing's constants (csrc/texture_point.h)
+TEX_BLOCK = 256
+TEX_LARGE_BOX = 256
+TEX_RUN = 4
+TEX_SUB = 16
+TEX_MIN_CELL = 4
+TEX_MAX_CELL = 64
+TEX_DEFAULT_CELL = 8
+TEX_MAX_ATLAS = 32768
+
 # the fusion's limits (csrc/fuse_point.h)
 FUSE_MAX_PAIRS = 32
 FUSE_BLOCK = 256
@@ -426,6 +456,15 @@ _MESH_OUT = [C.c_int64, C.c_int64, f32p, u8p, i32p]
 _MESH_EXTRACT = [C.POINTER(MeshGrid), f32p, u8p, u8p, u8p, C.POINTER(MeshOpts)] + _MESH_OUT + [C.POINTER(MeshStats)]
 _MESH_RECON = _TSDF_IN + [C.POINTER(TsdfOpts), C.POINTER(MeshOpts)] + _MESH_OUT + [f32p, u8p,
                                                                                   C.POINTER(MeshReconstructStats)]
+
+# the argument groups of the texturing entry points
+_TEX_IMG = [C.c_int32, i32p, i32p, i64p, u8p, f64p, f64p, f64p]
+_TEX_VIEWS = _TEX_IMG + [C.c_int64, f32p, C.c_int64, i32p, C.POINTER(MeshTextureOpts), i32p, i32p,
+                         C.POINTER(MeshFaceViewsStats)]
+_TEX_BAKE = _TEX_IMG + [C.c_int64, f32p, u8p, C.c_int64, i32p, i32p, C.POINTER(MeshTextureOpts), u8p, f32p,
+                        C.POINTER(MeshBakeStats)]
+_TEX_ALL = _TEX_IMG + [C.c_int64, f32p, u8p, C.c_int64, i32p, C.POINTER(MeshTextureOpts), i32p, i32p, u8p, f32p,
+                       C.POINTER(MeshTextureStats)]
 
 SIGNATURES = [
     ("sfm_version", C.c_char_p, []),
@@ -556,6 +595,16 @@ SIGNATURES = [
     ("sfm_mesh_reconstruct", C.c_int, [C.c_void_p] + _MESH_RECON),
     ("sfm_mesh_reconstruct_host", C.c_int, _MESH_RECON),
     ("sfm_mesh_write_ply", C.c_int, [C.c_char_p, C.c_int64, f32p, u8p, C.c_int64, i32p]),
+    ("sfm_mesh_texture_default_options", None, [C.POINTER(MeshTextureOpts)]),
+    ("sfm_mesh_atlas_fit", C.c_int, [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int32)]),
+    ("sfm_mesh_face_views", C.c_int, [C.c_void_p] + _TEX_VIEWS),
+    ("sfm_mesh_face_views_host", C.c_int, _TEX_VIEWS),
+    ("sfm_mesh_texture_bake", C.c_int, [C.c_void_p] + _TEX_BAKE),
+    ("sfm_mesh_texture_bake_host", C.c_int, _TEX_BAKE),
+    ("sfm_mesh_texture", C.c_int, [C.c_void_p] + _TEX_ALL),
+    ("sfm_mesh_texture_host", C.c_int, _TEX_ALL),
+    ("sfm_mesh_write_textured_ply", C.c_int, [C.c_char_p, C.c_char_p, C.c_int64, f32p, C.c_int64, i32p, f32p]),
     ("sfm_sift_options_default", None, [C.POINTER(SiftOptions)]),
     ("sfm_sift", C.c_int, [C.c_void_p, u8p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SiftOptions), C.c_int64,
                            f32p, u8p, i64p, C.POINTER(SiftSummary)]),

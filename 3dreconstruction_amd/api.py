@@ -1915,3 +1915,153 @@ def mesh_write_ply(path, V, tri, rgb=None):
     _check(abi.load().sfm_mesh_write_ply(_b(path), n, abi.ptr(V if n else np.zeros(3, np.float32), abi.f32p),
                                         abi.ptr(rgb if rgb is None or n else np.zeros(3, np.uint8), abi.u8p), m,
                                         abi.ptr(tri if m else np.zeros(3, np.int32), abi.i32p)), "sfm_mesh_write_ply")
+
+
+# ---- mesh texture ---------------------------------------------------------------------
+def mesh_texture_default_options():
+    o = abi.MeshTextureOpts()
+    abi.load().sfm_mesh_texture_default_options(C.byref(o))
+    return o
+
+
+def mesh_atlas_fit_raw(n_triangles, cell=abi.TEX_DEFAULT_CELL):
+    """sfm_mesh_atlas_fit without the check of its return code: (rc, W, H, cols)"""
+    W, H, cols = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = abi.load().sfm_mesh_atlas_fit(int(n_triangles), int(cell), C.byref(W), C.byref(H), C.byref(cols))
+    return rc, W.value, H.value, cols.value
+
+
+def mesh_atlas_fit(n_triangles, cell=abi.TEX_DEFAULT_CELL):
+    """sfm_mesh_atlas_fit: (W, H, cols) of the atlas of n_triangles faces"""
+    rc, W, H, cols = mesh_atlas_fit_raw(n_triangles, cell)
+    _check(rc, "sfm_mesh_atlas_fit")
+    return W, H, cols
+
+
+def _texture_inputs(wh, K, R, Cc, V, tri, images, pool, vertex_rgb=None):
+    wh = np.ascontiguousarray(np.asarray(wh, np.int32).reshape(-1))
+    n_img = len(wh) // 2
+    K = np.ascontiguousarray(np.asarray(K, np.float64).reshape(-1))
+    R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1))
+    Cc = np.ascontiguousarray(np.asarray(Cc, np.float64).reshape(-1))
+    assert len(K) == 9 * n_img and len(R) == 9 * n_img and len(Cc) == 3 * n_img
+    V = np.ascontiguousarray(np.asarray(V, np.float32).reshape(-1))
+    tri = np.ascontiguousarray(np.asarray(tri, np.int32).reshape(-1))
+    n_v, n_t = len(V) // 3, len(tri) // 3
+    colours = images is not None or pool is not None
+    channels, img_off, pixels = (pool if pool is not None else _pixel_pool(images)) if colours else (None, None, None)
+    if vertex_rgb is not None:
+        vertex_rgb = np.ascontiguousarray(np.asarray(vertex_rgb, np.uint8).reshape(-1))
+        assert len(vertex_rgb) == 3 * n_v
+    one = np.zeros(9)
+    keep = (wh, K, R, Cc, V, tri, channels, img_off, pixels, vertex_rgb, one)
+    img = (n_img, abi.ptr(wh if n_img else np.zeros(2, np.int32), abi.i32p), abi.ptr(channels, abi.i32p),
+           abi.ptr(img_off, abi.i64p), abi.ptr(pixels, abi.u8p), abi.ptr(K if n_img else one, abi.f64p),
+           abi.ptr(R if n_img else one, abi.f64p), abi.ptr(Cc if n_img else one, abi.f64p))
+    Vp = (n_v, abi.ptr(V if n_v else np.zeros(3, np.float32), abi.f32p))
+    tp = (n_t, abi.ptr(tri if n_t else np.zeros(3, np.int32), abi.i32p))
+    return img, Vp, abi.ptr(vertex_rgb, abi.u8p), tp, n_t, keep
+
+
+def _texture_cell(opts):
+    return int(opts.cell) if opts is not None else abi.TEX_DEFAULT_CELL
+
+
+def _atlas_arrays(n_t, opts, fill):
+    rc, W, H, _ = mesh_atlas_fit_raw(max(n_t, 0), _texture_cell(opts))
+    if rc != 0:
+        W = H = 0
+    return np.full(max(3 * W * H, 1), fill, np.uint8), np.full(max(6 * n_t, 1), fill, np.float32), W, H
+
+
+def mesh_face_views_raw(ctx, wh, K, R, Cc, V, tri, images=None, opts=None, pool=None, fill=0):
+    """sfm_mesh_face_views (ctx None: sfm_mesh_face_views_host) without the
+    check of its return code: (rc, face_view, face_pixels, stats dict); the
+    arrays are pre-filled with `fill`."""
+    lib = abi.load()
+    img, Vp, _, tp, n_t, keep = _texture_inputs(wh, K, R, Cc, V, tri, images, pool)
+    fv, fp = np.full(max(n_t, 1), fill, np.int32), np.full(max(n_t, 1), fill, np.int32)
+    st = abi.MeshFaceViewsStats()
+    args = img + Vp + tp + (C.byref(opts) if opts is not None else None, abi.ptr(fv, abi.i32p), abi.ptr(fp, abi.i32p),
+                            C.byref(st))
+    rc = lib.sfm_mesh_face_views_host(*args) if ctx is None else lib.sfm_mesh_face_views(ctx.h, *args)
+    return rc, fv[:n_t], fp[:n_t], _struct_dict(st)
+
+
+def mesh_face_views(ctx, wh, K, R, Cc, V, tri, images=None, opts=None, pool=None):
+    """sfm_mesh_face_views (ctx None: the host twin): dict(face_view, face_pixels
+    [n_triangles] int32, stats).  images as in undistort(): None entries are
+    skipped views; images None: every view counts."""
+    rc, fv, fp, st = mesh_face_views_raw(ctx, wh, K, R, Cc, V, tri, images, opts, pool)
+    _check(rc, "sfm_mesh_face_views_host" if ctx is None else "sfm_mesh_face_views")
+    return dict(face_view=fv, face_pixels=fp, stats=st)
+
+
+def mesh_texture_bake_raw(ctx, wh, K, R, Cc, V, tri, face_view, images=None, vertex_rgb=None, opts=None, pool=None,
+                          fill=0):
+    """sfm_mesh_texture_bake (ctx None: the host twin) without the check of its
+    return code: (rc, texture (flat), uv (flat), stats dict)."""
+    lib = abi.load()
+    img, Vp, vrgb, tp, n_t, keep = _texture_inputs(wh, K, R, Cc, V, tri, images, pool, vertex_rgb)
+    fv = np.ascontiguousarray(np.asarray(face_view, np.int32).reshape(-1))
+    assert len(fv) == n_t
+    tex, uv, W, H = _atlas_arrays(n_t, opts, fill)
+    st = abi.MeshBakeStats()
+    args = img + Vp + (vrgb,) + tp + (abi.ptr(fv if n_t else np.zeros(1, np.int32), abi.i32p),
+                                      C.byref(opts) if opts is not None else None, abi.ptr(tex, abi.u8p),
+                                      abi.ptr(uv, abi.f32p), C.byref(st))
+    rc = lib.sfm_mesh_texture_bake_host(*args) if ctx is None else lib.sfm_mesh_texture_bake(ctx.h, *args)
+    return rc, tex, uv, _struct_dict(st)
+
+
+def _texture_dict(tex, uv, n_t, st, W, H):
+    return dict(texture=tex[:3 * W * H].reshape(H, W, 3), uv=uv[:6 * n_t].reshape(-1, 3, 2), stats=st)
+
+
+def mesh_texture_bake(ctx, wh, K, R, Cc, V, tri, face_view, images=None, vertex_rgb=None, opts=None, pool=None):
+    """sfm_mesh_texture_bake (ctx None: the host twin) with the caller's
+    face_view: dict(texture [H, W, 3] uint8, top row first, uv [n, 3, 2], stats)."""
+    rc, tex, uv, st = mesh_texture_bake_raw(ctx, wh, K, R, Cc, V, tri, face_view, images, vertex_rgb, opts, pool)
+    _check(rc, "sfm_mesh_texture_bake_host" if ctx is None else "sfm_mesh_texture_bake")
+    return _texture_dict(tex, uv, len(np.asarray(tri).reshape(-1)) // 3, st, st["W"], st["H"])
+
+
+def mesh_texture_raw(ctx, wh, K, R, Cc, V, tri, images=None, vertex_rgb=None, opts=None, pool=None, fill=0,
+                     views=True):
+    """sfm_mesh_texture (ctx None: the host twin) without the check of its
+    return code: (rc, face_view, face_pixels, texture, uv, stats dict);
+    views=False: face_view and face_pixels are not fetched (None)."""
+    lib = abi.load()
+    img, Vp, vrgb, tp, n_t, keep = _texture_inputs(wh, K, R, Cc, V, tri, images, pool, vertex_rgb)
+    fv, fp = (np.full(max(n_t, 1), fill, np.int32), np.full(max(n_t, 1), fill, np.int32)) if views else (None, None)
+    tex, uv, W, H = _atlas_arrays(n_t, opts, fill)
+    st = abi.MeshTextureStats()
+    args = img + Vp + (vrgb,) + tp + (C.byref(opts) if opts is not None else None, abi.ptr(fv, abi.i32p),
+                                      abi.ptr(fp, abi.i32p), abi.ptr(tex, abi.u8p), abi.ptr(uv, abi.f32p), C.byref(st))
+    rc = lib.sfm_mesh_texture_host(*args) if ctx is None else lib.sfm_mesh_texture(ctx.h, *args)
+    return rc, (fv[:n_t] if views else None), (fp[:n_t] if views else None), tex, uv, _struct_dict(st)
+
+
+def mesh_texture(ctx, wh, K, R, Cc, V, tri, images=None, vertex_rgb=None, opts=None, pool=None, views=True):
+    """sfm_mesh_texture (ctx None: the host twin): face views and bake in one
+    call.  dict(texture, uv, stats, and with views=True face_view, face_pixels)."""
+    rc, fv, fp, tex, uv, st = mesh_texture_raw(ctx, wh, K, R, Cc, V, tri, images, vertex_rgb, opts, pool, views=views)
+    _check(rc, "sfm_mesh_texture_host" if ctx is None else "sfm_mesh_texture")
+    out = _texture_dict(tex, uv, len(np.asarray(tri).reshape(-1)) // 3, st, st["bake"]["W"], st["bake"]["H"])
+    if views:
+        out.update(face_view=fv, face_pixels=fp)
+    return out
+
+
+def mesh_write_textured_ply(path, texture_name, V, tri, uv):
+    """sfm_mesh_write_textured_ply: x y z, then per face the indices and six texture coordinates"""
+    V = np.ascontiguousarray(np.asarray(V, np.float32).reshape(-1, 3))
+    tri = np.ascontiguousarray(np.asarray(tri, np.int32).reshape(-1, 3))
+    uv = np.ascontiguousarray(np.asarray(uv, np.float32).reshape(-1, 6))
+    assert len(uv) == len(tri)
+    n, m = len(V), len(tri)
+    _check(abi.load().sfm_mesh_write_textured_ply(_b(path), _b(texture_name),
+                                                  n, abi.ptr(V if n else np.zeros(3, np.float32), abi.f32p), m,
+                                                  abi.ptr(tri if m else np.zeros(3, np.int32), abi.i32p),
+                                                  abi.ptr(uv if m else np.zeros(6, np.float32), abi.f32p)),
+           "sfm_mesh_write_textured_ply")

@@ -27,6 +27,9 @@
 //   MeshReconstructor     the first step of meshWork(): the filtered depth maps into a
 //                         TSDF volume and its zero level set as a Mesh (mesh.hpp;
 //                         sfm_tsdf_integrate, sfm_mesh_extract, sfm_mesh_reconstruct)
+//   MeshTexturer          the last step of meshWork(): per-face view choice and a texture
+//                         atlas (mesh.hpp; sfm_mesh_face_views, sfm_mesh_texture_bake,
+//                         sfm_mesh_texture; TexturedMesh is its product)
 //   SIFT_Image_describer  src/nonFree/sift/SIFT_describer.hpp and detectFeature()
 //                         (sparseBuilder.cpp:575-756) on 8-bit gray buffers
 //                         (sift.hpp; sfm_sift)
@@ -350,6 +353,37 @@ struct GpuMeshBackend {
     const char* last_error() const { return sfm_last_error(); }
 };
 using GpuMeshReconstructor = MeshReconstructor<GpuMeshBackend>;
+
+// ---------------------------------------------------------------------------
+// MeshTexturer (mesh.hpp) on the GPU: sfm_mesh_face_views, sfm_mesh_texture_bake,
+// sfm_mesh_texture
+// ---------------------------------------------------------------------------
+struct GpuTextureBackend {
+    Context* ctx;
+    int face_views(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                   const double* K, const double* R, const double* C, int64_t n_vertices, const float* V, int64_t n_triangles,
+                   const int32_t* tri, const sfm_mesh_texture_opts* opts, int32_t* face_view, int32_t* face_pixels,
+                   sfm_mesh_face_views_stats* stats) const {
+        return sfm_mesh_face_views(ctx->get(), n_img, wh, channels, img_off, pixels, K, R, C, n_vertices, V, n_triangles, tri,
+                                   opts, face_view, face_pixels, stats);
+    }
+    int bake(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+             const double* K, const double* R, const double* C, int64_t n_vertices, const float* V, const uint8_t* vertex_rgb,
+             int64_t n_triangles, const int32_t* tri, const int32_t* face_view, const sfm_mesh_texture_opts* opts,
+             uint8_t* texture, float* uv, sfm_mesh_bake_stats* stats) const {
+        return sfm_mesh_texture_bake(ctx->get(), n_img, wh, channels, img_off, pixels, K, R, C, n_vertices, V, vertex_rgb,
+                                     n_triangles, tri, face_view, opts, texture, uv, stats);
+    }
+    int texture(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off, const uint8_t* pixels,
+                const double* K, const double* R, const double* C, int64_t n_vertices, const float* V, const uint8_t* vertex_rgb,
+                int64_t n_triangles, const int32_t* tri, const sfm_mesh_texture_opts* opts, int32_t* face_view,
+                int32_t* face_pixels, uint8_t* texture, float* uv, sfm_mesh_texture_stats* stats) const {
+        return sfm_mesh_texture(ctx->get(), n_img, wh, channels, img_off, pixels, K, R, C, n_vertices, V, vertex_rgb, n_triangles,
+                                tri, opts, face_view, face_pixels, texture, uv, stats);
+    }
+    const char* last_error() const { return sfm_last_error(); }
+};
+using GpuMeshTexturer = MeshTexturer<GpuTextureBackend>;
 
 // ---------------------------------------------------------------------------
 // SIFT_Image_describer (sift.hpp) on the GPU: sfm_sift

@@ -14,7 +14,7 @@ all: $(LIB) oracle/liboracle.so tests/cpp/facade_test tests/cpp/plan_pool_test t
      tests/cpp/triangulate_host_test tests/cpp/tracks_test tests/cpp/tracks_facade_test tests/cpp/resect_test \
      tests/cpp/relpose_test tests/cpp/sift_test tests/cpp/recon_test tests/cpp/colorize_test \
      tests/cpp/batch_points_test tests/cpp/undistort_test tests/cpp/depthmap_test \
-     tests/cpp/depthfuse_test tests/cpp/mesh_test
+     tests/cpp/depthfuse_test tests/cpp/mesh_test tests/cpp/texture_test
 
 build/%.hip.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -141,3 +141,14 @@ MESH_HOST_SRCS := $(CSRC)/mesh.cpp $(DEPTHMAP_HOST_SRCS)
 tests/cpp/mesh_test: tests/cpp/mesh_test.cpp $(MESH_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(MESH_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY \
 	    -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(MESH_HOST_SRCS) -lpthread
+
+# the mesh texturing on the host backend: the host paths of csrc/texture.cpp
+# (checks, the atlas fit, the host twins of the view choice and the bake, the
+# textured PLY writer) over those of the mesh stage and the depth maps (its
+# thread pool), and the façade of include/sfm/mesh.hpp compiled in (no library,
+# no HIP runtime: host only).  texture.cpp switches contraction off itself.
+# TEXTURE_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
+TEXTURE_HOST_SRCS := $(CSRC)/texture.cpp $(MESH_HOST_SRCS)
+tests/cpp/texture_test: tests/cpp/texture_test.cpp $(TEXTURE_HOST_SRCS) $(HDRS)
+	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(TEXTURE_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY \
+	    -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(TEXTURE_HOST_SRCS) -lpthread

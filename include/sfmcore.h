@@ -2184,6 +2184,183 @@ int sfm_mesh_reconstruct_host(int32_t n_img, const int32_t* wh, const int32_t* c
 int sfm_mesh_write_ply(const char* path, int64_t n_vertices, const float* V, const uint8_t* rgb, int64_t n_triangles,
                        const int32_t* tri);
 
+/* ------------------------------------------------------------------------ */
+/* Mesh texture                                              */
+/* The last step of meshWork(): every face chooses the view that sees it     */
+/* best, and a texture atlas is baked from the chosen views.  OpenMVS's      */
+/* TextureMesh packs charts and optimises seams serially; this is a method   */
+/* without an order: a face's place in the atlas follows from its index, and */
+/* every face chooses alone.  The device, the host twin and a restatement    */
+/* give the same bytes.  Nothing is pinned to OpenMVS's numbers; this        */
+/* comment is the contract.                                                  */
+/*                                                                          */
+/* Float arithmetic as in "Dense depth maps": single IEEE operations in the  */
+/* order written, dot(a, b) = (a0 b0 + a1 b1) + a2 b2, M q has the rows      */
+/* dot(M_row, q); M = K R is worked out in double and rounded once, C is     */
+/* rounded once.  (float) of an int64 rounds to nearest even.                */
+/*                                                                          */
+/* Inputs: n_img, wh, channels, img_off, pixels, K, R, C as                  */
+/* sfm_tsdf_integrate takes them; an image with img_off < 0 is skipped       */
+/* entirely (no occluder pass, no candidate).  sfm_mesh_face_views reads no  */
+/* pixel bytes: with pixels NULL every image counts.  The mesh is            */
+/* V[3 n_vertices] float, tri[3 n_triangles] int32 and, optionally,          */
+/* vertex_rgb[3 n_vertices].  Pixel (px, py) has its centre at the integer   */
+/* position.                                                                 */
+/*                                                                          */
+/* 1. Face views.  The views are taken in ascending index order; a to c run  */
+/* per view.                                                                 */
+/* a. Per corner X of a face: q = X - C, h = M q, z = h2, x = h0 / z,        */
+/*    y = h1 / z.  The face is drawable in the view when its three z > 0 and */
+/*    its three |x|, |y| <= 1048576.0f (NaN fails).  Xi = (int64)floorf(x *  */
+/*    16.0f + 0.5f), Yi likewise.  A2 = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 -  */
+/*    Y0).  A2 == 0: the face covers nothing.  A2 < 0: corners 1 and 2 are   */
+/*    exchanged, with their z, for b and c, and A2 stands for -A2.           */
+/* b. Edge k runs from corner a = (k + 1) % 3 to b = (k + 2) % 3; E_k(P) =   */
+/*    (Xb - Xa)(Py - Ya) - (Yb - Ya)(Px - Xa) at P = (16 px, 16 py), in      */
+/*    int64.  A pixel is covered when for every k: E_k > 0, or E_k == 0 and  */
+/*    (Yb - Ya > 0, or Yb - Ya == 0 and Xb - Xa > 0).  So a pixel centre on  */
+/*    an edge that two faces share belongs to exactly one of them.  Only     */
+/*    pixels of the image count (the walk is over the bounding box, integer  */
+/*    ceiling of min / 16 to integer floor of max / 16, clipped).            */
+/* c. Every drawable face occludes, whichever way it looks.  Per covered     */
+/*    pixel: w_k = 1.0f / z_k, num = ((float)E0 * w0 + (float)E1 * w1) +     */
+/*    (float)E2 * w2, d = (float)A2 / num; the pixel keeps the minimum of    */
+/*    ((uint64)bits(d) << 32) | face: the nearest face, the lowest index on  */
+/*    equal depth, whatever the order of arrival.                            */
+/* d. covered(f, v) is the count of b, won(f, v) the number of those pixels  */
+/*    that kept f.  f is eligible in v when it is drawable, front-facing     */
+/*    (dot((V1 - V0) x (V2 - V0), C - V0) > 0, the cross product's           */
+/*    components n0 = e1_1 e2_2 - e1_2 e2_1, n1 = e1_2 e2_0 - e1_0 e2_2,     */
+/*    n2 = e1_0 e2_1 - e1_1 e2_0 as written, corners not exchanged), its     */
+/*    three unrounded (x, y) lie in [0, w - 1] x [0, h - 1], covered >= 1    */
+/*    and won == covered.  face_view[f] is the eligible view with the        */
+/*    largest covered, the lowest index on a tie, or -1; face_pixels[f] is   */
+/*    that covered, or 0.                                                    */
+/* Limits: a face that crosses the camera plane of a view does not occlude   */
+/* in it; a face that covers no pixel centre gets the fallback of 2; each    */
+/* face chooses alone, there is no seam smoothing.                           */
+/*                                                                          */
+/* 2. Atlas.  s = cell (4 .. 64), n_sq = (n_triangles + 1) / 2, cols the     */
+/* smallest integer with cols cols >= n_sq, rows = ceil(n_sq / cols) (both 0 */
+/* without triangles), W = cols s, H = rows s; W or H above 32768:           */
+/* SFM_ERR_UNSUPPORTED.  Face f lies in square f / 2, at column (f / 2) %    */
+/* cols and row (f / 2) / cols (origin ox = column s, oy = row s), and is    */
+/* half f % 2 of it.  Texel (a, b) of a square, 0 <= a, b < s, belongs to    */
+/* half 0 when a + b <= s - 2, else to half 1.  Corners 0, 1, 2 in texel     */
+/* units from the square's origin (a texel's centre is at + 0.5): half 0:    */
+/* (0.5, 0.5) (s - 2.5, 0.5) (0.5, s - 2.5); half 1: (s - 0.5, s - 0.5)      */
+/* (2.5, s - 0.5) (s - 0.5, 2.5).  Each half keeps a diagonal of             */
+/* extrapolated texels, so a bilinear fetch inside one face's triangle never */
+/* reads the other's.  Weights: half 0: l1 = (float)a / (float)(s - 3), l2   */
+/* = (float)b / (float)(s - 3); half 1: l1 = (float)(s - 1 - a) / (float)(s  */
+/* - 3), l2 = (float)(s - 1 - b) / (float)(s - 3).                           */
+/* A texel of a face with face_view = v >= 0: per component P = (V0 + l1 *   */
+/* (V1 - V0)) + l2 * (V2 - V0); q = P - C, h = M q, z = h2; unless z > 0 the */
+/* texel is fill; x = fminf(fmaxf(h0 / z, 0), w - 1), y likewise; gx =       */
+/* floorf(x), dx = x - gx, gx1 = min(gx + 1, w - 1), likewise in y; per      */
+/* channel top = p00 + dx * (p10 - p00), bot = p01 + dx * (p11 - p01), val = */
+/* top + dy * (bot - top), byte = (uint8_t)floorf(val + 0.5f); a 1-channel   */
+/* image is replicated.  A face with face_view -1: with vertex_rgb, per      */
+/* channel (c0 + l1 * (c1 - c0)) + l2 * (c2 - c0), clamped to [0, 255] and   */
+/* rounded the same way; without, fill.  A texel whose half has no face:     */
+/* fill.  texture[3 W H] has its top row first, as a PNM stores it.          */
+/* uv[6 n_triangles]: per corner k of face f (the vertex tri[3 f + k]) u =   */
+/* ((float)ox + cx) / (float)W, v = 1.0f - ((float)oy + cy) / (float)H.      */
+/*                                                                          */
+/* Checks, on the host before any device call (the host twins refuse the     */
+/* same calls): a null argument, a negative count, a non-positive image      */
+/* size, a triangle index outside [0, n_vertices), a face_view outside [-1,  */
+/* n_img) or naming a skipped image (or any image when pixels is NULL), a    */
+/* coordinate or camera that is not finite, cell outside 4 .. 64, channels   */
+/* other than 1 or 3 on a loaded image, negative device_bytes:               */
+/* SFM_ERR_INVALID_ARG.  An image of 2^31 pixels or more, n_triangles or     */
+/* n_vertices >= 2^31, the atlas's limit, a resident set beyond device_bytes */
+/* (the images' bytes where they are sampled, the views, the vertices and    */
+/* their colours, the triangles, 12 bytes a face, one identity buffer of 8   */
+/* bytes a pixel of the largest image, the texture and the uv):              */
+/* SFM_ERR_UNSUPPORTED.  n_triangles == 0 succeeds and writes nothing.       */
+/* ------------------------------------------------------------------------ */
+typedef struct sfm_mesh_texture_opts {
+    int32_t cell;            /* texels along a square's side, 4 .. 64; default 8 */
+    uint8_t fill[3];         /* texels without a source; default 0 0 0         */
+    uint8_t pad;
+    int64_t device_bytes;    /* budget for the resident set; 0: 4 GiB          */
+} sfm_mesh_texture_opts;
+/* [cpu] */
+void sfm_mesh_texture_default_options(sfm_mesh_texture_opts* opts);
+/* [cpu] W, H and cols of section 2. */
+int sfm_mesh_atlas_fit(int64_t n_triangles, int32_t cell, int32_t* W, int32_t* H, int32_t* cols);
+
+typedef struct sfm_mesh_face_views_stats {
+    int64_t n_textured;      /* faces with a view                              */
+    int64_t n_untextured;
+    int64_t n_not_drawable;  /* (face, view) pairs refused by step a           */
+    int64_t sum_pixels;      /* the sum of face_pixels: the mean tells a
+                                caller which cell to choose                    */
+    int64_t resident_bytes;
+    double seconds[3];       /* upload, kernels, download (HIP events).  Host
+                                twin: 0, the wall time, 0.                     */
+} sfm_mesh_face_views_stats;
+/* Section 1: face_view[n_triangles], face_pixels[n_triangles].  opts NULL =
+ * the defaults; stats may be NULL. */
+int sfm_mesh_face_views(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                        const uint8_t* pixels, const double* K, const double* R, const double* C, int64_t n_vertices,
+                        const float* V, int64_t n_triangles, const int32_t* tri, const sfm_mesh_texture_opts* opts,
+                        int32_t* face_view, int32_t* face_pixels, sfm_mesh_face_views_stats* stats);
+/* [cpu] the host twin (threads over faces, then over rows): the same bytes and counts */
+int sfm_mesh_face_views_host(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                             const uint8_t* pixels, const double* K, const double* R, const double* C, int64_t n_vertices,
+                             const float* V, int64_t n_triangles, const int32_t* tri, const sfm_mesh_texture_opts* opts,
+                             int32_t* face_view, int32_t* face_pixels, sfm_mesh_face_views_stats* stats);
+
+typedef struct sfm_mesh_bake_stats {
+    int32_t W, H, cols, pad; /* the atlas, as sfm_mesh_atlas_fit gives it      */
+    int64_t resident_bytes;
+    double seconds[3];
+} sfm_mesh_bake_stats;
+/* Section 2 with any face_view (the caller's choice, checked): texture[3 W H]
+ * and uv[6 n_triangles]; vertex_rgb may be NULL. */
+int sfm_mesh_texture_bake(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                          const uint8_t* pixels, const double* K, const double* R, const double* C, int64_t n_vertices,
+                          const float* V, const uint8_t* vertex_rgb, int64_t n_triangles, const int32_t* tri,
+                          const int32_t* face_view, const sfm_mesh_texture_opts* opts, uint8_t* texture, float* uv,
+                          sfm_mesh_bake_stats* stats);
+/* [cpu] the host twin (threads over rows of the atlas) */
+int sfm_mesh_texture_bake_host(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                               const uint8_t* pixels, const double* K, const double* R, const double* C, int64_t n_vertices,
+                               const float* V, const uint8_t* vertex_rgb, int64_t n_triangles, const int32_t* tri,
+                               const int32_t* face_view, const sfm_mesh_texture_opts* opts, uint8_t* texture, float* uv,
+                               sfm_mesh_bake_stats* stats);
+
+/* Section 1, then section 2, with face_view left on the device; face_view and
+ * face_pixels are downloaded only when non-NULL.  The outputs equal, byte for
+ * byte, those of the two calls chained.  The checks are the two calls'. */
+typedef struct sfm_mesh_texture_stats {
+    sfm_mesh_face_views_stats views;   /* the counts; seconds are 0 on the device */
+    sfm_mesh_bake_stats bake;          /* likewise                                */
+    int64_t resident_bytes;
+    double seconds[3];       /* upload, everything up to the last kernel,
+                                download.  Host twin: 0, the two calls' sum, 0 */
+} sfm_mesh_texture_stats;
+int sfm_mesh_texture(sfm_ctx* ctx, int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                     const uint8_t* pixels, const double* K, const double* R, const double* C, int64_t n_vertices,
+                     const float* V, const uint8_t* vertex_rgb, int64_t n_triangles, const int32_t* tri,
+                     const sfm_mesh_texture_opts* opts, int32_t* face_view, int32_t* face_pixels, uint8_t* texture, float* uv,
+                     sfm_mesh_texture_stats* stats);
+/* [cpu] the two host twins chained */
+int sfm_mesh_texture_host(int32_t n_img, const int32_t* wh, const int32_t* channels, const int64_t* img_off,
+                          const uint8_t* pixels, const double* K, const double* R, const double* C, int64_t n_vertices,
+                          const float* V, const uint8_t* vertex_rgb, int64_t n_triangles, const int32_t* tri,
+                          const sfm_mesh_texture_opts* opts, int32_t* face_view, int32_t* face_pixels, uint8_t* texture,
+                          float* uv, sfm_mesh_texture_stats* stats);
+/* [cpu] "ply / format binary_little_endian 1.0 / comment TextureFile <name> /
+ * element vertex n", float x y z, then "element face m / property list uchar
+ * int vertex_indices / property list uchar float texcoord": a byte 3 and three
+ * int32, then a byte 6 and six floats a face.  The texture itself is written
+ * with sfm_undistort_write_pnm (P6); image encoding stays outside the library. */
+int sfm_mesh_write_textured_ply(const char* path, const char* texture_name, int64_t n_vertices, const float* V,
+                                int64_t n_triangles, const int32_t* tri, const float* uv);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
