@@ -17,8 +17,6 @@ using namespace sfm;
 
 namespace {
 
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
-
 struct Masks {
     const uint8_t* pt_ok;
     const uint8_t* keep;

@@ -145,8 +145,6 @@ __global__ __launch_bounds__(kColorizeThreads) void colorize_colour_kernel(
     atomicSub(&state[kLeft], 1);
 }
 
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
-
 }  // namespace
 
 void colorize_device_assign(sfm_ctx* ctx, int32_t n_img, int32_t n_pt, int32_t n_obs, const ReconIndex& ix,

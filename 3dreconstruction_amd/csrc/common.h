@@ -202,6 +202,28 @@ struct PhaseTimer {
     }
 };
 
+// the monotonic clock in seconds (the host twins' stats)
+inline double seconds_now() { return PhaseTimer::now() * 1e-3; }
+
+// N events on a stream, for the seconds between them
+template <int N>
+struct StreamEvents {
+    hipEvent_t ev[N] = {};
+    StreamEvents() {
+        for (hipEvent_t& e : ev) SFM_HIP(hipEventCreate(&e));
+    }
+    ~StreamEvents() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void record(int p, hipStream_t s) { SFM_HIP(hipEventRecord(ev[p], s)); }
+    double between(int p, int q) const {
+        float ms = 0.f;
+        SFM_HIP(hipEventElapsedTime(&ms, ev[p], ev[q]));
+        return ms * 1e-3;
+    }
+};
+
 }  // namespace sfm
 
 struct sfm_ctx {

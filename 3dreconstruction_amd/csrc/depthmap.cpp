@@ -11,8 +11,6 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
-#include <functional>
-#include <thread>
 #include <vector>
 
 #include "depthmap.h"
@@ -20,20 +18,6 @@
 using namespace sfm;
 
 namespace sfm {
-
-// fn(item) for every item in [0, n), on up to 16 threads; returns when all are done
-void depth_parallel_for(size_t n, const std::function<void(size_t)>& fn) {
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t at; (at = next.fetch_add(1)) < n;) fn(at);
-    };
-    const unsigned hw = std::thread::hardware_concurrency();
-    const size_t n_threads = std::min<size_t>(std::min<size_t>(16, hw ? hw : 1), n);
-    std::vector<std::thread> pool;
-    for (size_t t = 1; t < n_threads; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-}
 
 static void mul33(const double* a, const double* b, double* o) {
     for (int r = 0; r < 3; ++r)
@@ -83,24 +67,19 @@ void depth_build_problem(const char* who, const DepthCameras& m, const int32_t* 
     std::vector<double> Kinv((size_t)9 * m.n_img, 0.0);
     P.views.resize((size_t)m.n_img);
     int64_t gray_bytes = 0;
-    for (int32_t i = 0; i < m.n_img; ++i) {
-        const int32_t w = m.wh[2 * i], h = m.wh[2 * i + 1];
-        SFM_REQUIRE(w > 0 && h > 0, SFM_ERR_INVALID_ARG, "%s: image %d has a non-positive size", who, i);
-        SFM_REQUIRE((int64_t)w * h < ((int64_t)1 << 31), SFM_ERR_UNSUPPORTED, "%s: image %d has 2^31 or more pixels", who, i);
+    // This stage's checks of image i run before the shared ones of image i + 1, as they always did: a
+    // later image of 2^31 pixels (SFM_ERR_UNSUPPORTED) does not hide an earlier SFM_ERR_INVALID_ARG.
+    // channels come with img_off (depth_prepare checks it); without pixels the first loaded image fails.
+    DenseImages D;
+    dense_images_prepare(who, m.n_img, m.wh, channels, img_off, channels ? pixels : nullptr, m.K, m.R, m.C, D, [&](int32_t i) {
+        const int32_t w = D.img[(size_t)i].w, h = D.img[(size_t)i].h;
         const int64_t n_nb = m.nb_off[i + 1] - m.nb_off[i];
         SFM_REQUIRE(n_nb >= 0, SFM_ERR_INVALID_ARG, "%s: nb_off decreases at image %d", who, i);
         SFM_REQUIRE(n_nb <= kDepthMaxNeighbors, SFM_ERR_INVALID_ARG, "%s: image %d has %lld neighbours, more than %d", who,
                     i, (long long)n_nb, kDepthMaxNeighbors);
         SFM_REQUIRE(n_nb == 0 || m.nb_view, SFM_ERR_INVALID_ARG, "%s: null nb_view", who);
         const bool loaded = !img_off || img_off[i] >= 0;
-        if (loaded && channels) {
-            SFM_REQUIRE(pixels, SFM_ERR_INVALID_ARG, "%s: null pixels", who);
-            SFM_REQUIRE(channels[i] == 1 || channels[i] == 3, SFM_ERR_INVALID_ARG, "%s: image %d has %d channels", who, i,
-                        channels[i]);
-        }
-        for (int a = 0; a < 9; ++a)
-            SFM_REQUIRE(std::isfinite(m.K[9 * i + a]) && std::isfinite(m.R[9 * i + a]) && std::isfinite(m.C[3 * i + a % 3]),
-                        SFM_ERR_INVALID_ARG, "%s: the camera of image %d is not finite", who, i);
+        SFM_REQUIRE(!(loaded && channels) || pixels, SFM_ERR_INVALID_ARG, "%s: null pixels", who);
         SFM_REQUIRE(inv33(m.K + 9 * i, &Kinv[9 * (size_t)i]), SFM_ERR_INVALID_ARG, "%s: K of image %d is singular", who, i);
         DepthView& V = P.views[(size_t)i];
         std::memset(&V, 0, sizeof V);
@@ -110,8 +89,7 @@ void depth_build_problem(const char* who, const DepthCameras& m, const int32_t* 
         V.nb0 = (int32_t)m.nb_off[i];
         V.nb1 = (int32_t)m.nb_off[i + 1];
         V.active = loaded && n_nb > 0;
-        V.map_off = P.n_map;
-        P.n_map += (int64_t)w * h;
+        V.map_off = D.img[(size_t)i].map_off;
         V.gray_off = -1;
         if (loaded && channels) {
             V.gray_off = gray_bytes;
@@ -130,7 +108,8 @@ void depth_build_problem(const char* who, const DepthCameras& m, const int32_t* 
             P.max_w = std::max(P.max_w, w);
             P.max_h = std::max(P.max_h, h);
         }
-    }
+    });
+    P.n_map = D.n_map;
     P.pairs.resize((size_t)m.nb_off[m.n_img]);
     for (int32_t i = 0; i < m.n_img; ++i)
         for (int64_t q = m.nb_off[i]; q < m.nb_off[i + 1]; ++q) {
@@ -154,7 +133,7 @@ void depth_build_problem(const char* who, const DepthCameras& m, const int32_t* 
     std::vector<int32_t> loaded;
     for (int32_t i = 0; i < m.n_img; ++i)
         if (P.views[(size_t)i].gray_off >= 0) loaded.push_back(i);
-    depth_parallel_for(loaded.size(), [&](size_t at) {
+    dense_parallel_for(loaded.size(), [&](size_t at) {
         const int32_t i = loaded[at];
         const DepthView& V = P.views[(size_t)i];
         const uint8_t* src = pixels + img_off[i];
@@ -231,8 +210,6 @@ void depth_init_maps(const DepthProblem& P, const float* init_depth, const float
 
 namespace {
 
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
-
 // rows of the active images, one item each
 struct RowItem {
     int32_t img, y;
@@ -256,7 +233,7 @@ void depthmap_host(const DepthProblem& P, const DepthParams& prm, bool init_give
         n = normal + 3 * V.map_off;
         c = cost + V.map_off;
     };
-    depth_parallel_for(items.size(), [&](size_t at) {
+    dense_parallel_for(items.size(), [&](size_t at) {
         const DepthView& V = P.views[(size_t)items[at].img];
         const DepthRef ref{gray + V.gray_off, V.w, 0, 0};
         const int32_t y = items[at].y;
@@ -275,7 +252,7 @@ void depthmap_host(const DepthProblem& P, const DepthParams& prm, bool init_give
     });
     for (int32_t it = 0; it < prm.iterations; ++it)
         for (int32_t colour = 0; colour < 2; ++colour)
-            depth_parallel_for(items.size(), [&](size_t at) {
+            dense_parallel_for(items.size(), [&](size_t at) {
                 const DepthView& V = P.views[(size_t)items[at].img];
                 const DepthRef ref{gray + V.gray_off, V.w, 0, 0};
                 const int32_t y = items[at].y;
@@ -303,7 +280,7 @@ void filter_host(const DepthProblem& P, const DepthFilterParams& prm, const floa
     const std::vector<RowItem> items = rows_of(P, false);
     std::vector<std::atomic<int64_t>> acc((size_t)2 * P.n_img);
     for (auto& a : acc) a = 0;
-    depth_parallel_for(items.size(), [&](size_t at) {
+    dense_parallel_for(items.size(), [&](size_t at) {
         const int32_t i = items[at].img, y = items[at].y;
         const DepthView& V = P.views[(size_t)i];
         const int32_t need = std::min(prm.min_consistent, V.nb1 - V.nb0);

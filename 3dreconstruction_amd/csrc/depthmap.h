@@ -3,10 +3,9 @@
 // depthmap.hip (the kernels and the launches) share.
 #pragma once
 #include <cstdint>
-#include <functional>
 #include <vector>
 
-#include "common.h"
+#include "dense_views.h"
 #include "depthmap_point.h"
 
 namespace sfm {
@@ -50,9 +49,7 @@ struct DepthCall {
     sfm_depthmap_stats st;
 };
 
-// depthmap.cpp, shared with fuse.cpp.  fn(item) for every item in [0, n), on up
-// to 16 threads.
-void depth_parallel_for(size_t n, const std::function<void(size_t)>& fn);
+// depthmap.cpp, shared with fuse.cpp.
 // A and b of the pair (reference i, neighbour j), in double, rounded once
 void depth_pair_matrices(const DepthCameras& m, int32_t i, int32_t j, float* A, float* b);
 // The checks that the estimation, the filter and the fusion share, and the views

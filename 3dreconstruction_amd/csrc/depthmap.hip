@@ -135,25 +135,6 @@ __global__ __launch_bounds__(256) void depth_filter_kernel(FilterLaunch a) {
     }
 }
 
-// the four events of a call: upload, kernels, download between them
-struct Events {
-    hipEvent_t ev[4] = {};
-    Events() {
-        for (hipEvent_t& e : ev) SFM_HIP(hipEventCreate(&e));
-    }
-    ~Events() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void seconds(double* s) const {
-        for (int p = 0; p < 3; ++p) {
-            float ms = 0.f;
-            SFM_HIP(hipEventElapsedTime(&ms, ev[p], ev[p + 1]));
-            s[p] = ms * 1e-3;
-        }
-    }
-};
-
 }  // namespace
 
 void depth_estimate_upload(hipStream_t s, const DepthProblem& P, bool init_given, const float* depth,
@@ -244,20 +225,20 @@ void depthmap_device(sfm_ctx* ctx, const DepthProblem& P, const DepthParams& prm
     hipStream_t s = ctx->stream;
     const size_t n_map = (size_t)P.n_map;
     DepthResident r;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     depth_estimate_upload(s, P, init_given, depth, normal, r);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     depth_estimate_launch(s, P, prm, init_given, r);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     unsigned long long at_worst = 0;
     SFM_HIP(hipMemcpyAsync(depth, r.depth.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
     SFM_HIP(hipMemcpyAsync(normal, r.normal.p, 3 * n_map * sizeof(float), hipMemcpyDeviceToHost, s));
     SFM_HIP(hipMemcpyAsync(cost, r.cost.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
     SFM_HIP(hipMemcpyAsync(&at_worst, r.count.p, sizeof at_worst, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     SFM_HIP(hipStreamSynchronize(s));
-    ev.seconds(seconds);
+    for (int p = 0; p < 3; ++p) seconds[p] = ev.between(p, p + 1);
     depth_estimate_counts(P, prm, at_worst, n_estimated, n_invalid);
 }
 
@@ -271,22 +252,22 @@ void depthmap_filter_device(sfm_ctx* ctx, const DepthProblem& P, const DepthFilt
     r.pairs.alloc(std::max<size_t>(P.pairs.size(), 1));
     r.depth.alloc(n_map);
     r.cost.alloc(n_map);
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     r.views.upload(P.views.data(), P.views.size(), s);
     r.pairs.upload(P.pairs.data(), P.pairs.size(), s);
     r.depth.upload(depth, n_map, s);
     r.cost.upload(cost, n_map, s);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     depth_filter_launch(s, P, prm, r);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     std::vector<unsigned long long> cnt((size_t)2 * P.n_img, 0);
     SFM_HIP(hipMemcpyAsync(depth_out, r.filtered.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
     SFM_HIP(hipMemcpyAsync(n_agree, r.agree.p, n_map, hipMemcpyDeviceToHost, s));
     SFM_HIP(hipMemcpyAsync(cnt.data(), r.fcounts.p, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     SFM_HIP(hipStreamSynchronize(s));
-    ev.seconds(seconds);
+    for (int p = 0; p < 3; ++p) seconds[p] = ev.between(p, p + 1);
     for (size_t k = 0; k < cnt.size(); ++k) counts[k] = (int64_t)cnt[k];
 }
 

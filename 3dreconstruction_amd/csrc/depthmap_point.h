@@ -9,11 +9,7 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define SFM_DEPTH_HD __host__ __device__
-#else
-#define SFM_DEPTH_HD
-#endif
+#include "dense_common.h"
 
 namespace sfm {
 
@@ -55,43 +51,36 @@ struct DepthFilterParams {
 struct DepthRef {
     const uint8_t* p;
     int32_t stride, ox, oy;
-    SFM_DEPTH_HD float at(int32_t x, int32_t y) const { return (float)p[(y - oy) * stride + (x - ox)]; }
+    SFM_HD float at(int32_t x, int32_t y) const { return (float)p[(y - oy) * stride + (x - ox)]; }
 };
 
-SFM_DEPTH_HD inline uint64_t depth_mix64(uint64_t z) {   // synth_rng.h's mix64
+SFM_HD inline uint64_t depth_mix64(uint64_t z) {   // synth_rng.h's mix64
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
     return z ^ (z >> 31);
 }
 // synth_rng.h's entity_seed(seed, image, pixel)
-SFM_DEPTH_HD inline uint64_t depth_pixel_seed(uint64_t seed, uint64_t img, uint64_t idx) {
+SFM_HD inline uint64_t depth_pixel_seed(uint64_t seed, uint64_t img, uint64_t idx) {
     return depth_mix64(depth_mix64(seed ^ (img * 0xD1B54A32D192ED03ULL)) + idx * 0x9E3779B97F4A7C15ULL);
 }
 // draw k of a pixel, in [0, 1)
-SFM_DEPTH_HD inline float depth_uniform(uint64_t base, uint32_t k) {
+SFM_HD inline float depth_uniform(uint64_t base, uint32_t k) {
     return (float)(depth_mix64(base + (uint64_t)k * 0x9E3779B97F4A7C15ULL) >> 40) * 0x1.0p-24f;
 }
 
-SFM_DEPTH_HD inline float depth_dot3(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-// M [x y 1]
-SFM_DEPTH_HD inline void depth_mul_pixel(const float* M, float x, float y, float* o) {
-    o[0] = (M[0] * x + M[1] * y) + M[2];
-    o[1] = (M[3] * x + M[4] * y) + M[5];
-    o[2] = (M[6] * x + M[7] * y) + M[8];
-}
 // n . (d ray): the plane's offset along its normal
-SFM_DEPTH_HD inline float depth_plane_offset(const float* n, float d, const float* ray) {
+SFM_HD inline float depth_plane_offset(const float* n, float d, const float* ray) {
     const float X[3] = {d * ray[0], d * ray[1], d * ray[2]};
-    return depth_dot3(n, X);
+    return dot3(n, X);
 }
-SFM_DEPTH_HD inline void depth_face_camera(float* n, const float* ray) {
-    if (depth_dot3(n, ray) > 0.0f) {
+SFM_HD inline void depth_face_camera(float* n, const float* ray) {
+    if (dot3(n, ray) > 0.0f) {
         n[0] = -n[0];
         n[1] = -n[1];
         n[2] = -n[2];
     }
 }
-SFM_DEPTH_HD inline void depth_normalize(float* v) {
+SFM_HD inline void depth_normalize(float* v) {
     const float len = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     v[0] = v[0] / len;
     v[1] = v[1] / len;
@@ -99,7 +88,7 @@ SFM_DEPTH_HD inline void depth_normalize(float* v) {
 }
 
 // Σa and Σaa of the reference patch (integers below 2^24: exact in any order)
-SFM_DEPTH_HD inline void depth_ref_sums(const DepthRef& ref, int32_t px, int32_t py, int32_t r, float* sa, float* saa) {
+SFM_HD inline void depth_ref_sums(const DepthRef& ref, int32_t px, int32_t py, int32_t r, float* sa, float* saa) {
     float s = 0.0f, ss = 0.0f;
     for (int32_t dy = -r; dy <= r; ++dy)
         for (int32_t dx = -r; dx <= r; ++dx) {
@@ -112,9 +101,9 @@ SFM_DEPTH_HD inline void depth_ref_sums(const DepthRef& ref, int32_t px, int32_t
 }
 
 // The cost of the plane (offset t = n . (d ray(p)), normal n) at pixel p against one neighbour.
-SFM_DEPTH_HD inline float depth_pair_cost(const DepthView& V, const DepthPair& Q, const uint8_t* gray, const DepthRef& ref,
-                                          int32_t px, int32_t py, int32_t r, float t, const float* n, float sa,
-                                          float saa) {
+SFM_HD inline float depth_pair_cost(const DepthView& V, const DepthPair& Q, const uint8_t* gray, const DepthRef& ref,
+                                    int32_t px, int32_t py, int32_t r, float t, const float* n, float sa,
+                                    float saa) {
     const uint8_t* img = gray + Q.gray_off;
     const int32_t side = 2 * r + 1;
     const float N = (float)(side * side);
@@ -126,20 +115,13 @@ SFM_DEPTH_HD inline float depth_pair_cost(const DepthView& V, const DepthPair& Q
         for (int32_t dx = -r; dx <= r; ++dx) {
             const float qx = (float)(px + dx), qy = (float)(py + dy);
             float rq[3], aq[3];
-            depth_mul_pixel(V.Ki, qx, qy, rq);
-            const float z = t / depth_dot3(n, rq);
-            depth_mul_pixel(Q.A, qx, qy, aq);
+            mul_pixel(V.Ki, qx, qy, rq);
+            const float z = t / dot3(n, rq);
+            mul_pixel(Q.A, qx, qy, aq);
             const float h0 = z * aq[0] + Q.b[0], h1 = z * aq[1] + Q.b[1], h2 = z * aq[2] + Q.b[2];
             const float x = h0 / h2, y = h1 / h2;
             if (!(z > 0.0f && h2 > 0.0f && x >= 0.0f && x <= xmax && y >= 0.0f && y <= ymax)) return kDepthWorstCost;
-            const float x0f = floorf(x), y0f = floorf(y);
-            const float fx = x - x0f, fy = y - y0f;
-            const int32_t x0 = (int32_t)x0f, y0 = (int32_t)y0f;
-            const int32_t x1 = x0 + 1 > Q.w - 1 ? Q.w - 1 : x0 + 1, y1 = y0 + 1 > Q.h - 1 ? Q.h - 1 : y0 + 1;
-            const uint8_t *row0 = img + (int64_t)y0 * Q.w, *row1 = img + (int64_t)y1 * Q.w;
-            const float g00 = (float)row0[x0], g10 = (float)row0[x1], g01 = (float)row1[x0], g11 = (float)row1[x1];
-            const float top = g00 + fx * (g10 - g00), bot = g01 + fx * (g11 - g01);
-            const float b = top + fy * (bot - top);
+            const float b = bilinear_u8(img, Q.w, Q.h, 1, 0, x, y);
             const float a = ref.at(px + dx, py + dy);
             sb += b;
             sbb += b * b;
@@ -155,9 +137,9 @@ SFM_DEPTH_HD inline float depth_pair_cost(const DepthView& V, const DepthPair& Q
 
 // The cost of the plane (d, n) at pixel p: the neighbours' costs ascending, the
 // first min(n_best, n_nb) averaged (summed in that order, then divided).
-SFM_DEPTH_HD inline float depth_cost(const DepthView& V, const DepthPair* pairs, const uint8_t* gray, const DepthRef& ref,
-                                     int32_t px, int32_t py, const float* rp, const DepthParams& prm, float d,
-                                     const float* n, float sa, float saa) {
+SFM_HD inline float depth_cost(const DepthView& V, const DepthPair* pairs, const uint8_t* gray, const DepthRef& ref,
+                               int32_t px, int32_t py, const float* rp, const DepthParams& prm, float d,
+                               const float* n, float sa, float saa) {
     const float t = depth_plane_offset(n, d, rp);
     float s[kDepthMaxNeighbors];
 #pragma unroll
@@ -181,7 +163,7 @@ SFM_DEPTH_HD inline float depth_cost(const DepthView& V, const DepthPair* pairs,
 }
 
 // the random plane of draws u[0..3): inverse depth uniform, normal towards the camera
-SFM_DEPTH_HD inline void depth_random_plane(const DepthView& V, const float* rp, const float* u, float* d, float* n) {
+SFM_HD inline void depth_random_plane(const DepthView& V, const float* rp, const float* u, float* d, float* n) {
     const float inv = V.imin + u[0] * (V.imax - V.imin);
     *d = 1.0f / inv;
     n[0] = 2.0f * u[1] - 1.0f;
@@ -192,8 +174,8 @@ SFM_DEPTH_HD inline void depth_random_plane(const DepthView& V, const float* rp,
 }
 
 // the plane (d, n) perturbed by delta with the draws u[0..4)
-SFM_DEPTH_HD inline void depth_perturbed_plane(const DepthView& V, const float* rp, float delta, const float* u, float d,
-                                               const float* n, float* d2, float* n2) {
+SFM_HD inline void depth_perturbed_plane(const DepthView& V, const float* rp, float delta, const float* u, float d,
+                                         const float* n, float* d2, float* n2) {
     float inv = 1.0f / d + (delta * (2.0f * u[0] - 1.0f)) * (V.imax - V.imin);
     if (inv < V.imin) inv = V.imin;
     if (inv > V.imax) inv = V.imax;
@@ -203,18 +185,18 @@ SFM_DEPTH_HD inline void depth_perturbed_plane(const DepthView& V, const float* 
     depth_face_camera(n2, rp);
 }
 
-SFM_DEPTH_HD inline bool depth_estimated(const DepthView& V, int32_t r, int32_t x, int32_t y) {
+SFM_HD inline bool depth_estimated(const DepthView& V, int32_t r, int32_t x, int32_t y) {
     return x >= r && x < V.w - r && y >= r && y < V.h - r;
 }
 
 // The initial plane of pixel p of image i and its cost.  depth / normal / cost
 // are the image's maps; with init_given the plane is read from them.
-SFM_DEPTH_HD inline void depth_init_pixel(const DepthView& V, const DepthPair* pairs, const uint8_t* gray,
-                                          const DepthRef& ref, const DepthParams& prm, bool init_given, int32_t i,
-                                          int32_t px, int32_t py, float* depth, float* normal, float* cost) {
+SFM_HD inline void depth_init_pixel(const DepthView& V, const DepthPair* pairs, const uint8_t* gray,
+                                    const DepthRef& ref, const DepthParams& prm, bool init_given, int32_t i,
+                                    int32_t px, int32_t py, float* depth, float* normal, float* cost) {
     const int64_t idx = (int64_t)py * V.w + px;
     float rp[3], sa, saa, d, n[3];
-    depth_mul_pixel(V.Ki, (float)px, (float)py, rp);
+    mul_pixel(V.Ki, (float)px, (float)py, rp);
     depth_ref_sums(ref, px, py, prm.r, &sa, &saa);
     if (init_given) {
         d = depth[idx];
@@ -233,12 +215,12 @@ SFM_DEPTH_HD inline void depth_init_pixel(const DepthView& V, const DepthPair* p
 // neighbours of the other colour, a perturbed plane, a fresh random plane; each
 // taken when strictly cheaper.  Reads planes of the other colour only and
 // writes its own.
-SFM_DEPTH_HD inline void depth_update_pixel(const DepthView& V, const DepthPair* pairs, const uint8_t* gray,
-                                            const DepthRef& ref, const DepthParams& prm, int32_t it, int32_t i,
-                                            int32_t px, int32_t py, float* depth, float* normal, float* cost) {
+SFM_HD inline void depth_update_pixel(const DepthView& V, const DepthPair* pairs, const uint8_t* gray,
+                                      const DepthRef& ref, const DepthParams& prm, int32_t it, int32_t i,
+                                      int32_t px, int32_t py, float* depth, float* normal, float* cost) {
     const int64_t idx = (int64_t)py * V.w + px;
     float rp[3], sa, saa;
-    depth_mul_pixel(V.Ki, (float)px, (float)py, rp);
+    mul_pixel(V.Ki, (float)px, (float)py, rp);
     depth_ref_sums(ref, px, py, prm.r, &sa, &saa);
     float d = depth[idx], n[3] = {normal[3 * idx], normal[3 * idx + 1], normal[3 * idx + 2]}, c = cost[idx];
     const int32_t ox[8] = {-1, 1, 0, 0, -5, 5, 0, 0}, oy[8] = {0, 0, -1, 1, 0, 0, -5, 5};
@@ -248,8 +230,8 @@ SFM_DEPTH_HD inline void depth_update_pixel(const DepthView& V, const DepthPair*
         const int64_t sidx = (int64_t)sy * V.w + sx;
         const float ns[3] = {normal[3 * sidx], normal[3 * sidx + 1], normal[3 * sidx + 2]};
         float rs[3];
-        depth_mul_pixel(V.Ki, (float)sx, (float)sy, rs);
-        const float dp = depth_plane_offset(ns, depth[sidx], rs) / depth_dot3(ns, rp);
+        mul_pixel(V.Ki, (float)sx, (float)sy, rs);
+        const float dp = depth_plane_offset(ns, depth[sidx], rs) / dot3(ns, rp);
         if (!(dp >= V.dmin && dp <= V.dmax)) continue;
         const float cc = depth_cost(V, pairs, gray, ref, px, py, rp, prm, dp, ns, sa, saa);
         if (cc < c) {
@@ -293,8 +275,8 @@ SFM_DEPTH_HD inline void depth_update_pixel(const DepthView& V, const DepthPair*
 
 // The consistency filter at pixel p: how many neighbours agree (-1: the pixel
 // is no candidate).  depth / cost are the maps of all images.
-SFM_DEPTH_HD inline int32_t depth_filter_pixel(const DepthView& V, const DepthPair* pairs, const DepthFilterParams& prm,
-                                               int32_t px, int32_t py, const float* depth, const float* cost) {
+SFM_HD inline int32_t depth_filter_pixel(const DepthView& V, const DepthPair* pairs, const DepthFilterParams& prm,
+                                         int32_t px, int32_t py, const float* depth, const float* cost) {
     const int64_t idx = V.map_off + (int64_t)py * V.w + px;
     const float d = depth[idx];
     if (!(d > 0.0f && cost[idx] <= prm.max_cost)) return -1;
@@ -302,11 +284,11 @@ SFM_DEPTH_HD inline int32_t depth_filter_pixel(const DepthView& V, const DepthPa
     for (int32_t q = V.nb0; q < V.nb1; ++q) {
         const DepthPair& Q = pairs[q];
         float ap[3];
-        depth_mul_pixel(Q.A, (float)px, (float)py, ap);
+        mul_pixel(Q.A, (float)px, (float)py, ap);
         const float h0 = d * ap[0] + Q.b[0], h1 = d * ap[1] + Q.b[1], z = d * ap[2] + Q.b[2];
-        const float x = floorf(h0 / z + 0.5f), y = floorf(h1 / z + 0.5f);
-        if (!(z > 0.0f && x >= 0.0f && x <= (float)(Q.w - 1) && y >= 0.0f && y <= (float)(Q.h - 1))) continue;
-        const float dj = depth[Q.map_off + (int64_t)(int32_t)y * Q.w + (int32_t)x];
+        const int64_t at = nearest_pixel(h0 / z, h1 / z, Q.w, Q.h);
+        if (!(z > 0.0f) || at < 0) continue;
+        const float dj = depth[Q.map_off + at];
         if (dj > 0.0f && fabsf(z - dj) <= prm.rel_tol * z) ++agree;
     }
     return agree;

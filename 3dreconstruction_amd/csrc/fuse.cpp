@@ -1,8 +1,8 @@
 // Depth-map fusion, host side (include/sfmcore.h, "Dense fusion"): the
-// argument checks, the fusion pair lists (the per-pair matrices are
-// depthmap.cpp's), the host twin (threads over rows: fates, a prefix over the
-// rows, points), the CSR expansion of the view lists, the PLY writer, and the
-// entry points over either backend, sfm_densify among them.  The kernels and
+// argument checks (the images': dense_views.cpp), the fusion pair lists, the host
+// twin (threads over rows: fates, a prefix over the rows, points), the CSR
+// expansion of the view lists, the cloud's PLY (dense_ply.cpp), and the entry
+// points over either backend, sfm_densify among them.  The kernels and
 // the transfers are fuse.hip's.  SFM_DEPTHMAP_HOST_ONLY leaves the device entry
 // points out (tests/cpp/depthfuse_test.cpp).
 #pragma clang fp contract(off)
@@ -11,15 +11,15 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
+#include "dense_ply.h"
 #include "fuse.h"
 
 using namespace sfm;
 
 namespace {
-
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
 
 // the fusion pair list of every image: lists[i] in list order, and what was dropped
 int64_t fusion_lists(int32_t n_img, const int64_t* nb_off, const int32_t* nb_view,
@@ -68,14 +68,14 @@ struct RowItem {
 void fuse_host(const FuseProblem& F, const float* depth, const float* normal, const uint8_t* pixels, const FuseOut& out,
                int64_t* n_points, int64_t* n_suppressed) {
     std::vector<RowItem> rows;
-    for (int32_t i = 0; i < F.n_img; ++i)
+    for (int32_t i = 0; i < F.images.n_img; ++i)
         for (int32_t y = 0; y < F.views[(size_t)i].h; ++y) rows.push_back(RowItem{i, y});
-    std::vector<uint32_t> mask((size_t)F.n_map);
-    std::vector<uint8_t> fate((size_t)F.n_map);
+    std::vector<uint32_t> mask((size_t)F.images.n_map);
+    std::vector<uint8_t> fate((size_t)F.images.n_map);
     std::vector<int64_t> base(rows.size() + 1, 0), supp(rows.size(), 0);
     const FuseView* views = F.views.data();
     const FusePair* pairs = F.pairs.data();
-    depth_parallel_for(rows.size(), [&](size_t at) {
+    dense_parallel_for(rows.size(), [&](size_t at) {
         const int32_t i = rows[at].img, y = rows[at].y;
         const FuseView& V = views[i];
         int64_t emitted = 0, suppressed = 0;
@@ -99,7 +99,7 @@ void fuse_host(const FuseProblem& F, const float* depth, const float* normal, co
     SFM_REQUIRE(*n_points <= out.cap_points, SFM_ERR_INVALID_ARG,
                 "sfm_depthmap_fuse_host: the cloud has %lld points, cap_points is %lld", (long long)*n_points,
                 (long long)out.cap_points);
-    depth_parallel_for(rows.size(), [&](size_t at) {
+    dense_parallel_for(rows.size(), [&](size_t at) {
         const int32_t i = rows[at].img, y = rows[at].y;
         const FuseView& V = views[i];
         int64_t rank = base[at];
@@ -135,9 +135,9 @@ int fuse(const char* who, sfm_ctx* ctx, bool device, int32_t n_img, const int32_
                  &st.resident_bytes);
     st.n_pairs_dropped = F.n_pairs_dropped;
     SFM_REQUIRE(out.cap_points >= 0, SFM_ERR_INVALID_ARG, "%s: negative cap_points", who);
-    SFM_REQUIRE(F.n_map == 0 || (depth && normal), SFM_ERR_INVALID_ARG, "%s: null depth or normal", who);
+    SFM_REQUIRE(F.images.n_map == 0 || (depth && normal), SFM_ERR_INVALID_ARG, "%s: null depth or normal", who);
     SFM_REQUIRE(out.cap_points == 0 || out.X, SFM_ERR_INVALID_ARG, "%s: null X", who);
-    if (F.n_map > 0) {
+    if (F.images.n_map > 0) {
         try {
             if (device) {
 #ifndef SFM_DEPTHMAP_HOST_ONLY
@@ -145,7 +145,7 @@ int fuse(const char* who, sfm_ctx* ctx, bool device, int32_t n_img, const int32_
 #endif
             } else {
                 const double t0 = seconds_now();
-                fuse_host(F, depth, normal, pixels ? pixels + F.pool_lo : nullptr, out, &st.n_points, &st.n_suppressed);
+                fuse_host(F, depth, normal, pixels ? pixels + F.images.pool_lo : nullptr, out, &st.n_points, &st.n_suppressed);
                 st.seconds[1] = seconds_now() - t0;
             }
         } catch (const SfmError&) {
@@ -204,41 +204,34 @@ void fuse_prepare(const char* who, const DepthCameras& m, const int32_t* channel
     // sizes, cameras, neighbours: the filter's checks (every image counts as loaded there)
     DepthProblem P;
     depth_build_problem(who, m, nullptr, nullptr, nullptr, nullptr, P);
-    F.n_img = m.n_img;
+    F.images.n_img = m.n_img;
     F.prm = FuseParams{o.rel_tol, o.min_normal_cos, o.min_normal_cos > -1.0f, pixels != nullptr};
     if (m.n_img <= 0) {
         *resident_bytes = 0;
         return;
     }
     SFM_REQUIRE(!pixels || (channels && img_off), SFM_ERR_INVALID_ARG, "%s: pixels without channels or img_off", who);
+    // the channels and the colour pool's window (sizes and cameras passed above)
+    dense_images_prepare(who, m.n_img, m.wh, channels, img_off, pixels, m.K, m.R, m.C, F.images);
     std::vector<std::vector<int32_t>> lists;
     F.n_pairs_dropped = fusion_lists(m.n_img, m.nb_off, m.nb_view, lists);
     F.views.resize((size_t)m.n_img);
-    F.n_map = P.n_map;
-    bool any = false;
     for (int32_t i = 0; i < m.n_img; ++i) {
-        const DepthView& D = P.views[(size_t)i];
+        const DenseImage& I = F.images.img[(size_t)i];
         FuseView& V = F.views[(size_t)i];
         std::memset(&V, 0, sizeof V);
         for (int a = 0; a < 9; ++a) {
-            V.Ki[a] = D.Ki[a];
+            V.Ki[a] = P.views[(size_t)i].Ki[a];
             V.R[a] = (float)m.R[9 * i + a];
         }
-        for (int a = 0; a < 3; ++a) V.C[a] = (float)m.C[3 * i + a];
-        V.w = D.w;
-        V.h = D.h;
-        V.map_off = D.map_off;
-        V.loaded = !pixels || img_off[i] >= 0;
+        dense_C(m.C, i, V.C);
+        V.w = I.w;
+        V.h = I.h;
+        V.map_off = I.map_off;
+        V.pix_off = I.pix_off;
+        V.loaded = I.loaded;
+        V.channels = I.channels;
         const int64_t n = (int64_t)V.w * V.h;
-        if (pixels && V.loaded) {
-            SFM_REQUIRE(channels[i] == 1 || channels[i] == 3, SFM_ERR_INVALID_ARG, "%s: image %d has %d channels", who, i,
-                        channels[i]);
-            V.channels = channels[i];
-            const int64_t lo = img_off[i], hi = img_off[i] + n * channels[i];
-            F.pool_lo = any ? std::min(F.pool_lo, lo) : lo;
-            F.pool_hi = any ? std::max(F.pool_hi, hi) : hi;
-            any = true;
-        }
         V.blk_off = F.n_blocks;
         const int64_t blocks = (n + kFuseBlock - 1) / kFuseBlock;
         F.n_blocks += blocks;
@@ -253,9 +246,8 @@ void fuse_prepare(const char* who, const DepthCameras& m, const int32_t* channel
         }
         V.p1 = (int32_t)F.pairs.size();
     }
-    // the colour bytes are uploaded from pool_lo on
-    for (FuseView& V : F.views) V.pix_off = V.channels ? img_off[&V - F.views.data()] - F.pool_lo : 0;
-    *resident_bytes = F.n_map * (int64_t)(4 * sizeof(float) + sizeof(uint32_t) + 1) + (F.pool_hi - F.pool_lo) +
+    *resident_bytes = F.images.n_map * (int64_t)(4 * sizeof(float) + sizeof(uint32_t) + 1) +
+                      (F.images.pool_hi - F.images.pool_lo) +
                       (int64_t)(F.views.size() * sizeof(FuseView) + F.pairs.size() * sizeof(FusePair)) +
                       F.n_blocks * (int64_t)(sizeof(int32_t) + sizeof(int64_t));
     const int64_t budget = o.device_bytes > 0 ? o.device_bytes : kFuseDefaultDeviceBytes;
@@ -322,29 +314,16 @@ extern "C" int sfm_dense_cloud_write_ply(const char* path, int64_t n_points, con
         const char* who = "sfm_dense_cloud_write_ply";
         SFM_REQUIRE(path && n_points >= 0 && (n_points == 0 || X), SFM_ERR_INVALID_ARG, "%s: null path or X, or negative n_points",
                     who);
-        std::FILE* f = std::fopen(path, "wb");
-        SFM_REQUIRE(f, SFM_ERR_INVALID_ARG, "%s: cannot open %s for writing", who, path);
-        std::fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\n", (long long)n_points);
-        std::fprintf(f, "property float x\nproperty float y\nproperty float z\n");
-        if (N) std::fprintf(f, "property float nx\nproperty float ny\nproperty float nz\n");
-        if (rgb) std::fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
-        std::fprintf(f, "end_header\n");
-        const size_t rec = 12 + (N ? 12 : 0) + (rgb ? 3 : 0);
-        std::vector<uint8_t> buf(rec * 4096);
-        for (int64_t k0 = 0; k0 < n_points; k0 += 4096) {
-            const int64_t k1 = std::min<int64_t>(k0 + 4096, n_points);
-            uint8_t* p = buf.data();
-            for (int64_t k = k0; k < k1; ++k) {
-                std::memcpy(p, X + 3 * k, 12);
-                p += 12;
-                if (N) std::memcpy(p, N + 3 * k, 12), p += 12;
-                if (rgb) std::memcpy(p, rgb + 3 * k, 3), p += 3;
-            }
-            std::fwrite(buf.data(), 1, (size_t)(p - buf.data()), f);
-        }
-        const bool bad = std::ferror(f) != 0;
-        const bool closed = std::fclose(f) == 0;
-        SFM_REQUIRE(!bad && closed, SFM_ERR_INVALID_ARG, "%s: writing %s failed", who, path);
+        std::string elements = "element vertex " + std::to_string(n_points) + "\nproperty float x\nproperty float y\nproperty float z\n";
+        if (N) elements += "property float nx\nproperty float ny\nproperty float nz\n";
+        if (rgb) elements += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+        PlyWriter ply(who, path, elements);
+        ply.records(n_points, 12 + (N ? 12 : 0) + (rgb ? 3 : 0), [&](int64_t k, uint8_t* p) {
+            std::memcpy(p, X + 3 * k, 12);
+            if (N) std::memcpy(p + 12, N + 3 * k, 12);
+            if (rgb) std::memcpy(p + (N ? 24 : 12), rgb + 3 * k, 3);
+        });
+        ply.close();
         return (int)SFM_OK;
     });
 }

@@ -1,6 +1,6 @@
 // Depth-map fusion (include/sfmcore.h, "Dense fusion"): what fuse.cpp (host:
-// checks, the fusion pair lists, the host twin, the CSR expansion, the PLY
-// writer) and fuse.hip (the kernels and the launches) share.
+// checks, the fusion pair lists, the host twin, the CSR expansion, the cloud's
+// PLY) and fuse.hip (the kernels and the launches) share.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -15,14 +15,12 @@ constexpr int64_t kFuseDefaultDeviceBytes = (int64_t)4 << 30;
 
 // What a fusion works on, checked and precomputed on the host (fuse.cpp).
 struct FuseProblem {
-    int32_t n_img = 0;
+    DenseImages images;               // sizes, maps, the colour pool's window
     std::vector<FuseView> views;      // [n_img]
     std::vector<FusePair> pairs;      // the fusion pair lists, image after image
-    int64_t n_map = 0;                // pixels of all maps
     int64_t n_blocks = 0;             // blocks of kFuseBlock pixels of all images
     int64_t max_blocks = 0;           // of one image
     int64_t n_pairs_dropped = 0;
-    int64_t pool_lo = 0, pool_hi = 0; // the bytes of the colour pool that loaded images cover
     FuseParams prm;
 };
 

@@ -10,10 +10,9 @@
 //          (wave64: 64 bits) and goes to block_count[image's first block +
 //          block]; the suppressed pixels are summed the same way and added
 //          with one integer atomic per workgroup (a count: order-free).
-//   scan   one workgroup: the exclusive prefix of block_count in (image,
-//          block) order, int64, 256 blocks a step (shuffles within a
-//          wavefront, the four wavefront sums through LDS); the total is read
-//          back once, to check cap_points and to size the download.
+//   scan   dense_scan.h's kernel over one array: the exclusive int64 prefix
+//          of block_count in (image, block) order; the total is read back
+//          once, to check cap_points and to size the download.
 //   emit   the same grid: a lane's rank is its block's base + the emitted
 //          counts of the wavefronts before it (LDS) + the popcount of its
 //          wavefront's ballot below it.  Emitting lanes gather their
@@ -25,12 +24,13 @@
 
 #include <algorithm>
 
+#include "dense_scan.h"
 #include "fuse.h"
 
 namespace sfm {
 namespace {
 
-static_assert(kFuseBlock == 256, "four wavefronts of 64 lanes");
+static_assert(kFuseBlock == kDenseBlock, "dense_scan.h's workgroup: four wavefronts of 64 lanes");
 
 struct FuseLaunch {
     const FuseView* views;
@@ -50,7 +50,7 @@ struct FuseLaunch {
 };
 
 __global__ __launch_bounds__(kFuseBlock) void fuse_mark_kernel(FuseLaunch a) {
-    __shared__ unsigned emitted[4], suppressed[4];
+    __shared__ int32_t emitted[4], suppressed[4];
     const int32_t i = (int32_t)blockIdx.y;
     const FuseView& V = a.views[i];
     const int64_t n = (int64_t)V.w * V.h, at = (int64_t)blockIdx.x * kFuseBlock + threadIdx.x;
@@ -63,61 +63,26 @@ __global__ __launch_bounds__(kFuseBlock) void fuse_mark_kernel(FuseLaunch a) {
         a.mask[V.map_off + at] = mask;
         a.fate[V.map_off + at] = (uint8_t)fate;
     }
-    const unsigned long long em = __ballot(fate == kFuseEmitted), su = __ballot(fate == kFuseSuppressed);
-    if ((threadIdx.x & 63) == 0) {
-        emitted[threadIdx.x >> 6] = (unsigned)__popcll(em);
-        suppressed[threadIdx.x >> 6] = (unsigned)__popcll(su);
-    }
-    __syncthreads();
+    int32_t n_emitted, n_suppressed;
+    block_ballot_rank(fate == kFuseEmitted, emitted, &n_emitted);
+    block_ballot_rank(fate == kFuseSuppressed, suppressed, &n_suppressed);
     if (threadIdx.x == 0) {
-        a.block_count[V.blk_off + blockIdx.x] = (int32_t)(emitted[0] + emitted[1] + emitted[2] + emitted[3]);
-        const unsigned s = suppressed[0] + suppressed[1] + suppressed[2] + suppressed[3];
-        if (s) atomicAdd(a.n_suppressed, (unsigned long long)s);
+        a.block_count[V.blk_off + blockIdx.x] = n_emitted;
+        if (n_suppressed) atomicAdd(a.n_suppressed, (unsigned long long)n_suppressed);
     }
-}
-
-// base[k] = count[0] + .. + count[k - 1]; base[n] = the total
-__global__ __launch_bounds__(kFuseBlock) void fuse_scan_kernel(const int32_t* count, int64_t n, int64_t* base) {
-    __shared__ int32_t wave_sum[4];
-    int64_t carry = 0;   // the same in every lane
-    for (int64_t k0 = 0; k0 < n; k0 += kFuseBlock) {
-        const int64_t k = k0 + threadIdx.x;
-        const int32_t v = k < n ? count[k] : 0;
-        int32_t incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t up = __shfl_up(incl, o);
-            if ((int)(threadIdx.x & 63) >= o) incl += up;
-        }
-        if ((threadIdx.x & 63) == 63) wave_sum[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        int32_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (w < (int)(threadIdx.x >> 6)) before += wave_sum[w];
-            all += wave_sum[w];
-        }
-        if (k < n) base[k] = carry + (int64_t)(before + incl - v);
-        carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) base[n] = carry;
 }
 
 __global__ __launch_bounds__(kFuseBlock) void fuse_emit_kernel(FuseLaunch a) {
-    __shared__ unsigned emitted[4];
+    __shared__ int32_t emitted[4];
     const int32_t i = (int32_t)blockIdx.y;
     const FuseView& V = a.views[i];
     const int64_t n = (int64_t)V.w * V.h, at = (int64_t)blockIdx.x * kFuseBlock + threadIdx.x;
     if ((int64_t)blockIdx.x * kFuseBlock >= n) return;   // the whole workgroup
     const bool emit = at < n && a.fate[V.map_off + at] == kFuseEmitted;
-    const unsigned long long em = __ballot(emit);
-    if ((threadIdx.x & 63) == 0) emitted[threadIdx.x >> 6] = (unsigned)__popcll(em);
-    __syncthreads();
+    int32_t n_emitted;
+    const int32_t before = block_ballot_rank(emit, emitted, &n_emitted);
     if (!emit) return;
-    int64_t rank = a.block_base[V.blk_off + blockIdx.x];
-    for (unsigned w = 0; w < (threadIdx.x >> 6); ++w) rank += emitted[w];
-    rank += __popcll(em & ((1ull << (threadIdx.x & 63)) - 1ull));
+    const int64_t rank = a.block_base[V.blk_off + blockIdx.x] + before;
     const int32_t px = (int32_t)(at % V.w), py = (int32_t)(at / V.w);
     const uint32_t mask = a.mask[V.map_off + at];
     float X[3], N[3];
@@ -134,22 +99,6 @@ __global__ __launch_bounds__(kFuseBlock) void fuse_emit_kernel(FuseLaunch a) {
     if (a.src_image) a.src_image[rank] = i;
     if (a.src_pixel) a.src_pixel[rank] = (int32_t)at;
 }
-
-struct Events {
-    hipEvent_t ev[6] = {};
-    Events() {
-        for (hipEvent_t& e : ev) SFM_HIP(hipEventCreate(&e));
-    }
-    ~Events() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    double between(int p, int q) const {
-        float ms = 0.f;
-        SFM_HIP(hipEventElapsedTime(&ms, ev[p], ev[q]));
-        return ms * 1e-3;
-    }
-};
 
 // The device side of a fusion whose maps are resident.
 struct FuseResident {
@@ -171,15 +120,15 @@ struct FuseResident {
 void fuse_upload(hipStream_t s, const FuseProblem& F, const uint8_t* pixels, FuseResident& r) {
     r.views.alloc(F.views.size());
     r.pairs.alloc(std::max<size_t>(F.pairs.size(), 1));
-    r.pool.alloc((size_t)std::max<int64_t>(F.pool_hi - F.pool_lo, 1));
-    r.mask.alloc((size_t)F.n_map);
-    r.fate.alloc((size_t)F.n_map);
+    r.pool.alloc((size_t)std::max<int64_t>(F.images.pool_hi - F.images.pool_lo, 1));
+    r.mask.alloc((size_t)F.images.n_map);
+    r.fate.alloc((size_t)F.images.n_map);
     r.block_count.alloc((size_t)F.n_blocks);
     r.block_base.alloc((size_t)F.n_blocks + 1);
     r.n_suppressed.alloc(1);
     r.views.upload(F.views.data(), F.views.size(), s);
     r.pairs.upload(F.pairs.data(), F.pairs.size(), s);
-    if (pixels) r.pool.upload(pixels + F.pool_lo, (size_t)(F.pool_hi - F.pool_lo), s);
+    if (pixels) r.pool.upload(pixels + F.images.pool_lo, (size_t)(F.images.pool_hi - F.images.pool_lo), s);
     r.n_suppressed.zero(s);
 }
 
@@ -199,8 +148,8 @@ void fuse_mark(hipStream_t s, const FuseProblem& F, const float* d_depth, const 
     a.block_base = r.block_base.p;
     a.n_suppressed = r.n_suppressed.p;
     a.prm = F.prm;
-    hipLaunchKernelGGL(fuse_mark_kernel, dim3((unsigned)F.max_blocks, (unsigned)F.n_img), dim3(kFuseBlock), 0, s, a);
-    hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(kFuseBlock), 0, s, r.block_count.p, F.n_blocks, r.block_base.p);
+    hipLaunchKernelGGL(fuse_mark_kernel, dim3((unsigned)F.max_blocks, (unsigned)F.images.n_img), dim3(kFuseBlock), 0, s, a);
+    hipLaunchKernelGGL(dense_scan_kernel, dim3(1), dim3(kDenseBlock), 0, s, r.block_count.p, F.n_blocks, r.block_base.p);
     SFM_HIP(hipGetLastError());
     int64_t total = 0;
     unsigned long long supp = 0;
@@ -223,7 +172,7 @@ void fuse_emit(hipStream_t s, const FuseProblem& F, const FuseOut& out, int64_t 
     if (out.view_mask) r.view_mask.alloc(n), a.view_mask = r.view_mask.p;
     if (out.src_image) r.src_image.alloc(n), a.src_image = r.src_image.p;
     if (out.src_pixel) r.src_pixel.alloc(n), a.src_pixel = r.src_pixel.p;
-    hipLaunchKernelGGL(fuse_emit_kernel, dim3((unsigned)F.max_blocks, (unsigned)F.n_img), dim3(kFuseBlock), 0, s, a);
+    hipLaunchKernelGGL(fuse_emit_kernel, dim3((unsigned)F.max_blocks, (unsigned)F.images.n_img), dim3(kFuseBlock), 0, s, a);
     SFM_HIP(hipGetLastError());
 }
 
@@ -250,25 +199,25 @@ void fuse_device(sfm_ctx* ctx, const FuseProblem& F, const float* depth, const f
                  const FuseOut& out, int64_t* n_points, int64_t* n_suppressed, double* seconds) {
     CtxScope scope_(ctx);
     hipStream_t s = ctx->stream;
-    const size_t n_map = (size_t)F.n_map;
+    const size_t n_map = (size_t)F.images.n_map;
     FuseResident r;
     DBuf<float> d_depth, d_normal;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<6> ev;
+    ev.record(0, s);
     d_depth.alloc(n_map);
     d_normal.alloc(3 * n_map);
     d_depth.upload(depth, n_map, s);
     d_normal.upload(normal, 3 * n_map, s);
     fuse_upload(s, F, pixels, r);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(1, s);
+    ev.record(2, s);
     fuse_mark(s, F, d_depth.p, d_normal.p, r, n_points, n_suppressed);
     require_cap("sfm_depthmap_fuse", *n_points, out);
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     fuse_emit(s, F, out, *n_points, r);
-    SFM_HIP(hipEventRecord(ev.ev[4], s));
+    ev.record(4, s);
     fuse_download(s, out, *n_points, r);
-    SFM_HIP(hipEventRecord(ev.ev[5], s));
+    ev.record(5, s);
     SFM_HIP(hipStreamSynchronize(s));
     seconds[0] = ev.between(0, 1);
     seconds[1] = ev.between(2, 3) + ev.between(3, 4);
@@ -291,17 +240,17 @@ void densify_device(sfm_ctx* ctx, const DepthCall& call, bool init_given, const 
     }
     DepthResident d;
     FuseResident r;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     depth_estimate_upload(s, P, init_given, h_depth.data(), h_normal.data(), d);
     fuse_upload(s, F, pixels, r);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     if (call.st.n_images > 0) depth_estimate_launch(s, P, call.prm, init_given, d);
     depth_filter_launch(s, P, fprm, d);
     fuse_mark(s, F, d.filtered.p, d.normal.p, r, &st->fuse.n_points, &st->fuse.n_suppressed);
     require_cap("sfm_densify", st->fuse.n_points, out);
     fuse_emit(s, F, out, st->fuse.n_points, r);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     fuse_download(s, out, st->fuse.n_points, r);
     unsigned long long at_worst = 0;
     std::vector<unsigned long long> cnt((size_t)2 * P.n_img, 0);
@@ -313,7 +262,7 @@ void densify_device(sfm_ctx* ctx, const DepthCall& call, bool init_given, const 
     if (maps.depth_filtered)
         SFM_HIP(hipMemcpyAsync(maps.depth_filtered, d.filtered.p, n_map * sizeof(float), hipMemcpyDeviceToHost, s));
     if (maps.n_agree) SFM_HIP(hipMemcpyAsync(maps.n_agree, d.agree.p, n_map, hipMemcpyDeviceToHost, s));
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     SFM_HIP(hipStreamSynchronize(s));
     for (int p = 0; p < 3; ++p) st->seconds[p] = ev.between(p, p + 1);
     if (call.st.n_images > 0)

@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "depthmap_point.h"
+#include "dense_common.h"
 
 namespace sfm {
 
@@ -37,38 +37,37 @@ struct FuseParams {
     int32_t use_normal, use_color;
 };
 
-SFM_DEPTH_HD inline float fuse_depth_at(const FuseView& V, const float* depth, int64_t idx) {
+SFM_HD inline float fuse_depth_at(const FuseView& V, const float* depth, int64_t idx) {
     return V.loaded ? depth[V.map_off + idx] : 0.0f;
 }
 // N = R' n
-SFM_DEPTH_HD inline void fuse_world_normal(const FuseView& V, const float* normal, int64_t idx, float* N) {
+SFM_HD inline void fuse_world_normal(const FuseView& V, const float* normal, int64_t idx, float* N) {
     const float* n = normal + 3 * (V.map_off + idx);
     for (int c = 0; c < 3; ++c) N[c] = (V.R[c] * n[0] + V.R[3 + c] * n[1]) + V.R[6 + c] * n[2];
 }
 // Xw = R' (d * (Ki [p 1])) + C
-SFM_DEPTH_HD inline void fuse_world_point(const FuseView& V, int32_t px, int32_t py, float d, float* X) {
+SFM_HD inline void fuse_world_point(const FuseView& V, int32_t px, int32_t py, float d, float* X) {
     float ray[3];
-    depth_mul_pixel(V.Ki, (float)px, (float)py, ray);
+    mul_pixel(V.Ki, (float)px, (float)py, ray);
     const float c0 = d * ray[0], c1 = d * ray[1], c2 = d * ray[2];
     for (int c = 0; c < 3; ++c) X[c] = ((V.R[c] * c0 + V.R[3 + c] * c1) + V.R[6 + c] * c2) + V.C[c];
 }
 
 // Pixel p of the reference at depth d against the pair Q whose image is J: the
 // pixel q of J it falls on (its raster index, or -1) and its depth z there.
-SFM_DEPTH_HD inline int64_t fuse_project(const FusePair& Q, const FuseView& J, int32_t px, int32_t py, float d, float* z) {
+SFM_HD inline int64_t fuse_project(const FusePair& Q, const FuseView& J, int32_t px, int32_t py, float d, float* z) {
     float ap[3];
-    depth_mul_pixel(Q.A, (float)px, (float)py, ap);
+    mul_pixel(Q.A, (float)px, (float)py, ap);
     const float h0 = d * ap[0] + Q.b[0], h1 = d * ap[1] + Q.b[1], h2 = d * ap[2] + Q.b[2];
-    const float x = floorf(h0 / h2 + 0.5f), y = floorf(h1 / h2 + 0.5f);
     *z = h2;
-    if (!(h2 > 0.0f && x >= 0.0f && x <= (float)(J.w - 1) && y >= 0.0f && y <= (float)(J.h - 1))) return -1;
-    return (int64_t)(int32_t)y * J.w + (int32_t)x;
+    const int64_t q = nearest_pixel(h0 / h2, h1 / h2, J.w, J.h);
+    return h2 > 0.0f ? q : -1;
 }
 
 // Does pair Q agree with pixel idx of V at depth d?  qidx: the pixel of J.
-SFM_DEPTH_HD inline bool fuse_agrees(const FuseView* views, const FuseView& V, const FusePair& Q, const FuseParams& prm,
-                                     int32_t px, int32_t py, int64_t idx, float d, const float* depth,
-                                     const float* normal, int64_t* qidx) {
+SFM_HD inline bool fuse_agrees(const FuseView* views, const FuseView& V, const FusePair& Q, const FuseParams& prm,
+                               int32_t px, int32_t py, int64_t idx, float d, const float* depth,
+                               const float* normal, int64_t* qidx) {
     const FuseView& J = views[Q.view];
     float z;
     const int64_t q = fuse_project(Q, J, px, py, d, &z);
@@ -80,15 +79,15 @@ SFM_DEPTH_HD inline bool fuse_agrees(const FuseView* views, const FuseView& V, c
         float Ni[3], Nj[3];
         fuse_world_normal(V, normal, idx, Ni);
         fuse_world_normal(J, normal, q, Nj);
-        if (!(depth_dot3(Ni, Nj) >= prm.min_normal_cos)) return false;
+        if (!(dot3(Ni, Nj) >= prm.min_normal_cos)) return false;
     }
     return true;
 }
 
 // The agreement mask and the fate of pixel (px, py) of image i.
-SFM_DEPTH_HD inline int32_t fuse_pixel_fate(const FuseView* views, const FusePair* pairs, const FuseParams& prm, int32_t i,
-                                            int32_t px, int32_t py, const float* depth, const float* normal,
-                                            uint32_t* mask_out) {
+SFM_HD inline int32_t fuse_pixel_fate(const FuseView* views, const FusePair* pairs, const FuseParams& prm, int32_t i,
+                                      int32_t px, int32_t py, const float* depth, const float* normal,
+                                      uint32_t* mask_out) {
     const FuseView& V = views[i];
     const int64_t idx = (int64_t)py * V.w + px;
     const float d = fuse_depth_at(V, depth, idx);
@@ -106,25 +105,12 @@ SFM_DEPTH_HD inline int32_t fuse_pixel_fate(const FuseView* views, const FusePai
     return !(d > 0.0f) ? kFuseNone : (lower ? kFuseSuppressed : kFuseEmitted);
 }
 
-SFM_DEPTH_HD inline void fuse_add_color(const FuseView& V, const uint8_t* pixels, int64_t idx, uint32_t* s) {
-    const uint8_t* p = pixels + V.pix_off + idx * V.channels;
-    if (V.channels == 3) {
-        s[0] += p[0];
-        s[1] += p[1];
-        s[2] += p[2];
-    } else {
-        s[0] += p[0];
-        s[1] += p[0];
-        s[2] += p[0];
-    }
-}
-
 // The fused point of an emitted pixel from its agreement mask; returns m.
 // rgb is written only when prm.use_color.
-SFM_DEPTH_HD inline int32_t fuse_pixel_point(const FuseView* views, const FusePair* pairs, const FuseParams& prm, int32_t i,
-                                             int32_t px, int32_t py, uint32_t mask, const float* depth,
-                                             const float* normal, const uint8_t* pixels, float* X, float* N,
-                                             uint8_t* rgb) {
+SFM_HD inline int32_t fuse_pixel_point(const FuseView* views, const FusePair* pairs, const FuseParams& prm, int32_t i,
+                                       int32_t px, int32_t py, uint32_t mask, const float* depth,
+                                       const float* normal, const uint8_t* pixels, float* X, float* N,
+                                       uint8_t* rgb) {
     const FuseView& V = views[i];
     const int64_t idx = (int64_t)py * V.w + px;
     const float d = fuse_depth_at(V, depth, idx);
@@ -135,7 +121,7 @@ SFM_DEPTH_HD inline int32_t fuse_pixel_point(const FuseView* views, const FusePa
     sn[0] = own[0];
     sn[1] = own[1];
     sn[2] = own[2];
-    if (prm.use_color) fuse_add_color(V, pixels, idx, col);
+    if (prm.use_color) add_color(pixels + V.pix_off + idx * V.channels, V.channels, col);
     int32_t m = 1;
     for (uint32_t rest = mask; rest; rest &= rest - 1) {
         const int32_t k = __builtin_ctz(rest);
@@ -150,7 +136,7 @@ SFM_DEPTH_HD inline int32_t fuse_pixel_point(const FuseView* views, const FusePa
             sx[c] = sx[c] + xj[c];
             sn[c] = sn[c] + nj[c];
         }
-        if (prm.use_color) fuse_add_color(J, pixels, q, col);
+        if (prm.use_color) add_color(pixels + J.pix_off + q * J.channels, J.channels, col);
         ++m;
     }
     const float fm = (float)m;
@@ -158,7 +144,7 @@ SFM_DEPTH_HD inline int32_t fuse_pixel_point(const FuseView* views, const FusePa
     const float len = sqrtf((sn[0] * sn[0] + sn[1] * sn[1]) + sn[2] * sn[2]);
     for (int c = 0; c < 3; ++c) N[c] = len > 0.0f ? sn[c] / len : own[c];
     if (prm.use_color)
-        for (int c = 0; c < 3; ++c) rgb[c] = (uint8_t)((2u * col[c] + (uint32_t)m) / (2u * (uint32_t)m));
+        for (int c = 0; c < 3; ++c) rgb[c] = mean_u8(col[c], (uint32_t)m);
     return m;
 }
 

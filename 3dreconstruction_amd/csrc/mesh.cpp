@@ -1,24 +1,24 @@
-// The mesh stage, host side (include/sfmcore.h, "Mesh"): the argument checks,
-// the grid fit, the per-image matrices, the host twins (threads over rows of
-// the lattice: integration; marks, a prefix over the points, vertices and
-// triangles), the PLY writer and the entry points over either backend.  The
-// kernels and the transfers are mesh.hip's.  SFM_DEPTHMAP_HOST_ONLY leaves the
-// device entry points out (tests/cpp/mesh_test.cpp).
+// The mesh stage, host side (include/sfmcore.h, "Mesh"): the argument checks
+// (the images': dense_views.cpp), the grid fit, the host twins (threads over
+// rows of the lattice: integration; marks, a prefix over the points, vertices
+// and triangles), the mesh's PLY (dense_ply.cpp) and the entry points over
+// either backend.  The kernels and the transfers are mesh.hip's.  SFM_DEPTHMAP_HOST_ONLY
+// leaves the device entry points out (tests/cpp/mesh_test.cpp).
 #pragma clang fp contract(off)
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
+#include "dense_ply.h"
 #include "mesh.h"
 
 using namespace sfm;
 
 namespace {
-
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
 
 void prepare_grid(const char* who, const sfm_mesh_grid* grid, MeshGrid& g, int64_t* n_vox) {
     SFM_REQUIRE(grid, SFM_ERR_INVALID_ARG, "%s: null grid", who);
@@ -54,47 +54,23 @@ void prepare_tsdf(const char* who, int32_t n_img, const int32_t* wh, const int32
     SFM_REQUIRE(n_img >= 0, SFM_ERR_INVALID_ARG, "%s: negative n_img", who);
     SFM_REQUIRE(n_img == 0 || (wh && K && R && C), SFM_ERR_INVALID_ARG, "%s: null argument", who);
     SFM_REQUIRE(!pixels || (channels && img_off), SFM_ERR_INVALID_ARG, "%s: pixels without channels or img_off", who);
-    P.n_img = n_img;
-    P.colours = pixels != nullptr;
+    dense_images_prepare(who, n_img, wh, channels, img_off, pixels, K, R, C, P.images);
     P.views.resize((size_t)n_img);
-    bool any = false;
     for (int32_t i = 0; i < n_img; ++i) {
-        const int32_t w = wh[2 * i], h = wh[2 * i + 1];
-        SFM_REQUIRE(w > 0 && h > 0, SFM_ERR_INVALID_ARG, "%s: image %d has a non-positive size", who, i);
-        SFM_REQUIRE((int64_t)w * h < ((int64_t)1 << 31), SFM_ERR_UNSUPPORTED, "%s: image %d has 2^31 or more pixels", who, i);
-        for (int a = 0; a < 9; ++a)
-            SFM_REQUIRE(std::isfinite(K[9 * i + a]) && std::isfinite(R[9 * i + a]) && std::isfinite(C[3 * i + a % 3]),
-                        SFM_ERR_INVALID_ARG, "%s: the camera of image %d is not finite", who, i);
+        const DenseImage& I = P.images.img[(size_t)i];
         MeshView& V = P.views[(size_t)i];
         std::memset(&V, 0, sizeof V);
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) {
-                const double* k = K + 9 * i + 3 * r;
-                const double* rr = R + 9 * i + c;
-                V.M[3 * r + c] = (float)(k[0] * rr[0] + k[1] * rr[3] + k[2] * rr[6]);
-            }
-        for (int a = 0; a < 3; ++a) V.C[a] = (float)C[3 * i + a];
-        V.w = w;
-        V.h = h;
-        V.map_off = P.n_map;
-        V.loaded = !pixels || img_off[i] >= 0;
-        const int64_t n = (int64_t)w * h;
-        P.n_map += n;
-        if (pixels && V.loaded) {
-            SFM_REQUIRE(channels[i] == 1 || channels[i] == 3, SFM_ERR_INVALID_ARG, "%s: image %d has %d channels", who, i,
-                        channels[i]);
-            V.channels = channels[i];
-            const int64_t lo = img_off[i], hi = img_off[i] + n * channels[i];
-            P.pool_lo = any ? std::min(P.pool_lo, lo) : lo;
-            P.pool_hi = any ? std::max(P.pool_hi, hi) : hi;
-            any = true;
-        }
+        dense_KR(K, R, i, V.M);
+        dense_C(C, i, V.C);
+        V.w = I.w;
+        V.h = I.h;
+        V.channels = I.channels;
+        V.loaded = I.loaded;
+        V.map_off = I.map_off;
+        V.pix_off = I.pix_off;
     }
-    // the colour bytes are uploaded from pool_lo on
-    for (int32_t i = 0; i < n_img; ++i)
-        P.views[(size_t)i].pix_off = P.views[(size_t)i].channels ? img_off[i] - P.pool_lo : 0;
-    SFM_REQUIRE(P.n_map == 0 || depth, SFM_ERR_INVALID_ARG, "%s: null depth", who);
-    *resident_bytes = P.n_map * (int64_t)sizeof(float) + (P.pool_hi - P.pool_lo) +
+    SFM_REQUIRE(P.images.n_map == 0 || depth, SFM_ERR_INVALID_ARG, "%s: null depth", who);
+    *resident_bytes = P.images.n_map * (int64_t)sizeof(float) + (P.images.pool_hi - P.images.pool_lo) +
                       (int64_t)(P.views.size() * sizeof(MeshView)) + P.n_vox * 9 +
                       mesh_blocks(P.n_vox) * (int64_t)(sizeof(int32_t) + sizeof(int64_t));
     const int64_t budget = o.device_bytes > 0 ? o.device_bytes : kMeshDefaultDeviceBytes;
@@ -129,13 +105,13 @@ void tsdf_host(const MeshProblem& P, const float* depth, const uint8_t* pixels, 
     const MeshGrid& g = P.g;
     const size_t rows = (size_t)g.ny * g.nz;
     std::vector<int64_t> seen(rows, 0);
-    depth_parallel_for(rows, [&](size_t row) {
+    dense_parallel_for(rows, [&](size_t row) {
         const int32_t j = (int32_t)(row % (size_t)g.ny), k = (int32_t)(row / (size_t)g.ny);
         int64_t n = 0;
         for (int32_t i = 0; i < g.nx; ++i) {
             const int64_t at = mesh_raster(g, i, j, k);
             uint8_t c[3] = {0, 0, 0}, has = 0;
-            const int32_t wgt = mesh_integrate_point(P.views.data(), P.n_img, g, P.trunc, depth, pixels, i, j, k, &tsdf[at], c, &has);
+            const int32_t wgt = mesh_integrate_point(P.views.data(), P.images.n_img, g, P.trunc, depth, pixels, i, j, k, &tsdf[at], c, &has);
             weight[at] = (uint8_t)wgt;
             n += wgt > 0;
             if (pixels) {
@@ -156,7 +132,7 @@ void extract_host(const char* who, const MeshGrid& g, int64_t n_vox, int32_t min
     std::vector<uint8_t> mask((size_t)n_vox), ntri((size_t)n_vox);
     std::vector<int32_t> vert_base((size_t)n_vox);
     std::vector<int64_t> row_v(rows + 1, 0), row_t(rows + 1, 0), row_d(rows, 0);
-    depth_parallel_for(rows, [&](size_t row) {
+    dense_parallel_for(rows, [&](size_t row) {
         const int32_t j = (int32_t)(row % (size_t)g.ny), k = (int32_t)(row / (size_t)g.ny);
         int64_t nv = 0, nt = 0, nd = 0;
         for (int32_t i = 0; i < g.nx; ++i) {
@@ -183,7 +159,7 @@ void extract_host(const char* who, const MeshGrid& g, int64_t n_vox, int32_t min
     st->n_triangles = row_t[rows];
     mesh_require_indexable(who, st->n_vertices);
     mesh_require_caps(who, *st, out);
-    depth_parallel_for(rows, [&](size_t row) {
+    dense_parallel_for(rows, [&](size_t row) {
         const int32_t j = (int32_t)(row % (size_t)g.ny), k = (int32_t)(row / (size_t)g.ny);
         int64_t rank = row_v[row];
         for (int32_t i = 0; i < g.nx; ++i) {
@@ -198,7 +174,7 @@ void extract_host(const char* who, const MeshGrid& g, int64_t n_vox, int32_t min
                 }
         }
     });
-    depth_parallel_for(rows, [&](size_t row) {
+    dense_parallel_for(rows, [&](size_t row) {
         const int32_t j = (int32_t)(row % (size_t)g.ny), k = (int32_t)(row / (size_t)g.ny);
         int64_t rank = row_t[row];
         for (int32_t i = 0; i < g.nx; ++i) {
@@ -225,7 +201,7 @@ int integrate(const char* who, sfm_ctx* ctx, bool device, int32_t n_img, const i
 #endif
     } else {
         const double t0 = seconds_now();
-        tsdf_host(P, depth, pixels ? pixels + P.pool_lo : nullptr, tsdf, weight, rgb, has_rgb, &st.n_observed);
+        tsdf_host(P, depth, pixels ? pixels + P.images.pool_lo : nullptr, tsdf, weight, rgb, has_rgb, &st.n_observed);
         st.seconds[1] = seconds_now() - t0;
     }
     if (stats) *stats = st;
@@ -381,40 +357,20 @@ extern "C" int sfm_mesh_write_ply(const char* path, int64_t n_vertices, const fl
         const char* who = "sfm_mesh_write_ply";
         SFM_REQUIRE(path && n_vertices >= 0 && n_triangles >= 0 && (n_vertices == 0 || V) && (n_triangles == 0 || tri),
                     SFM_ERR_INVALID_ARG, "%s: null path, V or tri, or a negative count", who);
-        for (int64_t k = 0; k < 3 * n_triangles; ++k)
-            SFM_REQUIRE(tri[k] >= 0 && tri[k] < n_vertices, SFM_ERR_INVALID_ARG, "%s: triangle %lld names vertex %d of %lld",
-                        who, (long long)(k / 3), tri[k], (long long)n_vertices);
-        std::FILE* f = std::fopen(path, "wb");
-        SFM_REQUIRE(f, SFM_ERR_INVALID_ARG, "%s: cannot open %s for writing", who, path);
-        std::fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\n", (long long)n_vertices);
-        std::fprintf(f, "property float x\nproperty float y\nproperty float z\n");
-        if (rgb) std::fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
-        std::fprintf(f, "element face %lld\nproperty list uchar int vertex_indices\nend_header\n", (long long)n_triangles);
-        const size_t rec = 12 + (rgb ? 3 : 0);
-        std::vector<uint8_t> buf(std::max<size_t>(rec, 13) * 4096);
-        for (int64_t k0 = 0; k0 < n_vertices; k0 += 4096) {
-            const int64_t k1 = std::min<int64_t>(k0 + 4096, n_vertices);
-            uint8_t* p = buf.data();
-            for (int64_t k = k0; k < k1; ++k) {
-                std::memcpy(p, V + 3 * k, 12);
-                p += 12;
-                if (rgb) std::memcpy(p, rgb + 3 * k, 3), p += 3;
-            }
-            std::fwrite(buf.data(), 1, (size_t)(p - buf.data()), f);
-        }
-        for (int64_t k0 = 0; k0 < n_triangles; k0 += 4096) {
-            const int64_t k1 = std::min<int64_t>(k0 + 4096, n_triangles);
-            uint8_t* p = buf.data();
-            for (int64_t k = k0; k < k1; ++k) {
-                *p++ = 3;
-                std::memcpy(p, tri + 3 * k, 12);
-                p += 12;
-            }
-            std::fwrite(buf.data(), 1, (size_t)(p - buf.data()), f);
-        }
-        const bool bad = std::ferror(f) != 0;
-        const bool closed = std::fclose(f) == 0;
-        SFM_REQUIRE(!bad && closed, SFM_ERR_INVALID_ARG, "%s: writing %s failed", who, path);
+        require_triangles(who, n_triangles, tri, n_vertices);
+        PlyWriter ply(who, path,
+                      "element vertex " + std::to_string(n_vertices) + "\nproperty float x\nproperty float y\nproperty float z\n" +
+                          (rgb ? "property uchar red\nproperty uchar green\nproperty uchar blue\n" : "") + "element face " +
+                          std::to_string(n_triangles) + "\nproperty list uchar int vertex_indices\n");
+        ply.records(n_vertices, 12 + (rgb ? 3 : 0), [&](int64_t k, uint8_t* p) {
+            std::memcpy(p, V + 3 * k, 12);
+            if (rgb) std::memcpy(p + 12, rgb + 3 * k, 3);
+        });
+        ply.records(n_triangles, 13, [&](int64_t k, uint8_t* p) {
+            p[0] = 3;
+            std::memcpy(p + 1, tri + 3 * k, 12);
+        });
+        ply.close();
         return (int)SFM_OK;
     });
 }

@@ -1,11 +1,11 @@
 // The mesh stage (include/sfmcore.h, "Mesh"): what mesh.cpp (host: checks, the
-// grid fit, the host twins, the PLY writer) and mesh.hip (the kernels and the
+// grid fit, the host twins, the mesh's PLY) and mesh.hip (the kernels and the
 // launches) share.
 #pragma once
 #include <cstdint>
 #include <vector>
 
-#include "depthmap.h"
+#include "dense_views.h"
 #include "mesh_point.h"
 
 namespace sfm {
@@ -20,11 +20,8 @@ static_assert(sizeof(MeshGrid) == sizeof(sfm_mesh_grid), "MeshGrid is sfm_mesh_g
 
 // What an integration works on, checked and precomputed on the host (mesh.cpp).
 struct MeshProblem {
-    int32_t n_img = 0;
+    DenseImages images;               // sizes, maps, the colour pool's window
     std::vector<MeshView> views;      // [n_img]
-    int64_t n_map = 0;                // pixels of all maps
-    int64_t pool_lo = 0, pool_hi = 0; // the bytes of the colour pool that loaded images cover
-    bool colours = false;
     MeshGrid g{};
     int64_t n_vox = 0;
     float trunc = 0.0f;

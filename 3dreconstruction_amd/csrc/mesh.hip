@@ -17,9 +17,8 @@
 //              a byte each; the workgroup's totals (vertices, triangles,
 //              degenerate triangles) come from a wavefront reduction
 //              (shuffles, then LDS) and go to three block_count arrays.
-//   scan       one workgroup per array: the exclusive int64 prefix of its
-//              block counts, 256 blocks a step (shuffles within a wavefront,
-//              the four wavefront sums through LDS); the totals are read back
+//   scan       dense_scan.h's kernel, one workgroup per array: the exclusive
+//              int64 prefix of its block counts; the totals are read back
 //              once, to check the caps and to size the download.
 //   vertex     a lane's rank is its block's base + the prefix inside the
 //              workgroup over the lanes' popcounts; writes vert_base[point]
@@ -31,12 +30,13 @@
 
 #include <algorithm>
 
+#include "dense_scan.h"
 #include "mesh.h"
 
 namespace sfm {
 namespace {
 
-static_assert(kMeshBlock == 256 && kMeshTileX * kMeshTileY == kMeshBlock, "four wavefronts of 64 lanes");
+static_assert(kMeshBlock == kDenseBlock && kMeshTileX * kMeshTileY == kMeshBlock, "dense_scan.h's workgroup");
 
 struct TsdfLaunch {
     const MeshView* views;
@@ -51,7 +51,7 @@ struct TsdfLaunch {
 };
 
 __global__ __launch_bounds__(kMeshBlock) void tsdf_integrate_kernel(TsdfLaunch a) {
-    __shared__ unsigned seen[4];
+    __shared__ int32_t seen[4];
     const int32_t i = (int32_t)(blockIdx.x * kMeshTileX + (threadIdx.x & (kMeshTileX - 1)));
     const int32_t j = (int32_t)(blockIdx.y * kMeshTileY + (threadIdx.x >> 6));
     const int32_t k = (int32_t)blockIdx.z;
@@ -70,12 +70,9 @@ __global__ __launch_bounds__(kMeshBlock) void tsdf_integrate_kernel(TsdfLaunch a
             a.has_rgb[at] = has;
         }
     }
-    const unsigned long long ob = __ballot(wgt > 0);
-    if ((threadIdx.x & 63) == 0) seen[threadIdx.x >> 6] = (unsigned)__popcll(ob);
-    __syncthreads();
-    if (threadIdx.x == 0)
-        a.obs_count[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] =
-            (int32_t)(seen[0] + seen[1] + seen[2] + seen[3]);
+    int32_t n_seen;
+    block_ballot_rank(wgt > 0, seen, &n_seen);
+    if (threadIdx.x == 0) a.obs_count[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = n_seen;
 }
 
 struct MeshLaunch {
@@ -92,28 +89,6 @@ struct MeshLaunch {
     int64_t n_vox, n_blocks;
     int32_t min_weight;
 };
-
-// the lane's own value removed from the inclusive sum over the workgroup's
-// lanes before and at it; *total: the workgroup's sum (LDS: four wavefront sums)
-__device__ inline int32_t block_exclusive(int32_t v, int32_t* wave_sum, int32_t* total) {
-    int32_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t up = __shfl_up(incl, o);
-        if ((int)(threadIdx.x & 63) >= o) incl += up;
-    }
-    if ((threadIdx.x & 63) == 63) wave_sum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    int32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        if (w < (int)(threadIdx.x >> 6)) before += wave_sum[w];
-        all += wave_sum[w];
-    }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
 
 __global__ __launch_bounds__(kMeshBlock) void mesh_mark_kernel(MeshLaunch a) {
     __shared__ int32_t wave_sum[3][4];
@@ -141,22 +116,6 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_mark_kernel(MeshLaunch a) {
     if (threadIdx.x < 3)
         a.block_count[threadIdx.x * a.n_blocks + blockIdx.x] =
             (wave_sum[threadIdx.x][0] + wave_sum[threadIdx.x][1]) + (wave_sum[threadIdx.x][2] + wave_sum[threadIdx.x][3]);
-}
-
-// array blockIdx.x: base[k] = count[0] + .. + count[k - 1]; base[n] = the total
-__global__ __launch_bounds__(kMeshBlock) void mesh_scan_kernel(const int32_t* count, int64_t n, int64_t* base) {
-    __shared__ int32_t wave_sum[4];
-    count += (int64_t)blockIdx.x * n;
-    base += (int64_t)blockIdx.x * (n + 1);
-    int64_t carry = 0;   // the same in every lane
-    for (int64_t k0 = 0; k0 < n; k0 += kMeshBlock) {
-        const int64_t k = k0 + threadIdx.x;
-        int32_t all;
-        const int32_t before = block_exclusive(k < n ? count[k] : 0, wave_sum, &all);
-        if (k < n) base[k] = carry + (int64_t)before;
-        carry += all;
-    }
-    if (threadIdx.x == 0) base[n] = carry;
 }
 
 __global__ __launch_bounds__(kMeshBlock) void mesh_vertex_kernel(MeshLaunch a) {
@@ -197,22 +156,6 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_triangle_kernel(MeshLaunch a)
     mesh_cell_triangles(a.g, a.tsdf, a.vert_base, a.mask, i, j, k, a.tri + 3 * rank);
 }
 
-struct Events {
-    hipEvent_t ev[4] = {};
-    Events() {
-        for (hipEvent_t& e : ev) SFM_HIP(hipEventCreate(&e));
-    }
-    ~Events() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    double between(int p, int q) const {
-        float ms = 0.f;
-        SFM_HIP(hipEventElapsedTime(&ms, ev[p], ev[q]));
-        return ms * 1e-3;
-    }
-};
-
 // the volume of a call on the device
 struct Volume {
     DBuf<float> tsdf;
@@ -240,12 +183,12 @@ void tsdf_upload(hipStream_t s, const MeshProblem& P, const float* depth, const 
                  Volume& vol) {
     const size_t n = (size_t)P.n_vox;
     r.views.alloc(std::max<size_t>(P.views.size(), 1));
-    r.depth.alloc((size_t)std::max<int64_t>(P.n_map, 1));
+    r.depth.alloc((size_t)std::max<int64_t>(P.images.n_map, 1));
     r.views.upload(P.views.data(), P.views.size(), s);
-    r.depth.upload(depth, (size_t)P.n_map, s);
+    r.depth.upload(depth, (size_t)P.images.n_map, s);
     if (pixels) {
-        r.pool.alloc((size_t)std::max<int64_t>(P.pool_hi - P.pool_lo, 1));
-        r.pool.upload(pixels + P.pool_lo, (size_t)(P.pool_hi - P.pool_lo), s);
+        r.pool.alloc((size_t)std::max<int64_t>(P.images.pool_hi - P.images.pool_lo, 1));
+        r.pool.upload(pixels + P.images.pool_lo, (size_t)(P.images.pool_hi - P.images.pool_lo), s);
         vol.rgb.alloc(3 * n);
         vol.has_rgb.alloc(n);
     }
@@ -270,9 +213,9 @@ void tsdf_launch(hipStream_t s, const MeshProblem& P, TsdfResident& r, Volume& v
     a.obs_count = r.obs_count.p;
     a.g = P.g;
     a.trunc = P.trunc;
-    a.n_img = P.n_img;
+    a.n_img = P.images.n_img;
     hipLaunchKernelGGL(tsdf_integrate_kernel, grid, dim3(kMeshBlock), 0, s, a);
-    hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kMeshBlock), 0, s, r.obs_count.p, r.n_groups, r.obs_base.p);
+    hipLaunchKernelGGL(dense_scan_kernel, dim3(1), dim3(kDenseBlock), 0, s, r.obs_count.p, r.n_groups, r.obs_base.p);
     SFM_HIP(hipGetLastError());
 }
 
@@ -311,7 +254,7 @@ void mesh_mark(hipStream_t s, const MeshGrid& g, int64_t n_vox, int32_t min_weig
     a.n_blocks = nb;
     a.min_weight = min_weight;
     hipLaunchKernelGGL(mesh_mark_kernel, dim3((unsigned)nb), dim3(kMeshBlock), 0, s, a);
-    hipLaunchKernelGGL(mesh_scan_kernel, dim3(3), dim3(kMeshBlock), 0, s, r.block_count.p, nb, r.block_base.p);
+    hipLaunchKernelGGL(dense_scan_kernel, dim3(3), dim3(kDenseBlock), 0, s, r.block_count.p, nb, r.block_base.p);
     SFM_HIP(hipGetLastError());
     int64_t totals[3] = {0, 0, 0};
     for (int q = 0; q < 3; ++q)
@@ -358,14 +301,14 @@ void tsdf_device(sfm_ctx* ctx, const MeshProblem& P, const float* depth, const u
     hipStream_t s = ctx->stream;
     TsdfResident r;
     Volume vol;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     tsdf_upload(s, P, depth, pixels, r, vol);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     tsdf_launch(s, P, r, vol);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     volume_download(s, P.n_vox, vol, tsdf, weight, rgb, has_rgb);
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     *n_observed = read_observed(s, r);
     for (int p = 0; p < 3; ++p) seconds[p] = ev.between(p, p + 1);
 }
@@ -378,8 +321,8 @@ void mesh_extract_device(sfm_ctx* ctx, const MeshGrid& g, int32_t min_weight, co
     const size_t n = (size_t)n_vox;
     Volume vol;
     MeshResident r;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     vol.tsdf.alloc(n);
     vol.weight.alloc(n);
     vol.tsdf.upload(tsdf, n, s);
@@ -390,14 +333,14 @@ void mesh_extract_device(sfm_ctx* ctx, const MeshGrid& g, int32_t min_weight, co
         vol.rgb.upload(rgb, 3 * n, s);
         vol.has_rgb.upload(has_rgb, n, s);
     }
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     mesh_mark(s, g, n_vox, min_weight, vol.tsdf.p, vol.weight.p, vol.rgb.p, vol.has_rgb.p, r, st);
     mesh_require_indexable("sfm_mesh_extract", st->n_vertices);
     mesh_require_caps("sfm_mesh_extract", *st, out);
     mesh_emit(s, out, *st, r);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     mesh_download(s, out, *st, r);
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     SFM_HIP(hipStreamSynchronize(s));
     for (int p = 0; p < 3; ++p) st->seconds[p] = ev.between(p, p + 1);
 }
@@ -410,20 +353,20 @@ void mesh_reconstruct_device(sfm_ctx* ctx, const MeshProblem& P, const float* de
     TsdfResident t;
     Volume vol;
     MeshResident r;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     tsdf_upload(s, P, depth, pixels, t, vol);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     tsdf_launch(s, P, t, vol);
     mesh_mark(s, P.g, P.n_vox, min_weight, vol.tsdf.p, vol.weight.p, vol.rgb.p, vol.has_rgb.p, r, &st->mesh);
     st->tsdf.n_observed = read_observed(s, t);
     mesh_require_indexable("sfm_mesh_reconstruct", st->mesh.n_vertices);
     mesh_require_caps("sfm_mesh_reconstruct", st->mesh, out);
     mesh_emit(s, out, st->mesh, r);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     mesh_download(s, out, st->mesh, r);
     volume_download(s, P.n_vox, vol, tsdf, weight, nullptr, nullptr);
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     SFM_HIP(hipStreamSynchronize(s));
     for (int p = 0; p < 3; ++p) st->seconds[p] = ev.between(p, p + 1);
 }

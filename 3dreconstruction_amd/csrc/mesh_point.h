@@ -9,7 +9,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "depthmap_point.h"
+#include "dense_common.h"
 
 namespace sfm {
 
@@ -30,10 +30,10 @@ struct MeshGrid {
     int32_t nx, ny, nz, pad;
 };
 
-SFM_DEPTH_HD inline int64_t mesh_raster(const MeshGrid& g, int32_t i, int32_t j, int32_t k) {
+SFM_HD inline int64_t mesh_raster(const MeshGrid& g, int32_t i, int32_t j, int32_t k) {
     return ((int64_t)k * g.ny + j) * g.nx + i;
 }
-SFM_DEPTH_HD inline void mesh_position(const MeshGrid& g, int32_t i, int32_t j, int32_t k, float* X) {
+SFM_HD inline void mesh_position(const MeshGrid& g, int32_t i, int32_t j, int32_t k, float* X) {
     X[0] = g.origin[0] + (float)i * g.voxel;
     X[1] = g.origin[1] + (float)j * g.voxel;
     X[2] = g.origin[2] + (float)k * g.voxel;
@@ -42,9 +42,9 @@ SFM_DEPTH_HD inline void mesh_position(const MeshGrid& g, int32_t i, int32_t j, 
 // ---- integration ----------------------------------------------------------------------
 // Lattice point (i, j, k) against the images in index order.  rgb / has_rgb are
 // written only when pixels is given.  Returns the point's weight.
-SFM_DEPTH_HD inline int32_t mesh_integrate_point(const MeshView* views, int32_t n_img, const MeshGrid& g, float trunc,
-                                                 const float* depth, const uint8_t* pixels, int32_t i, int32_t j,
-                                                 int32_t k, float* tsdf, uint8_t* rgb, uint8_t* has_rgb) {
+SFM_HD inline int32_t mesh_integrate_point(const MeshView* views, int32_t n_img, const MeshGrid& g, float trunc,
+                                           const float* depth, const uint8_t* pixels, int32_t i, int32_t j,
+                                           int32_t k, float* tsdf, uint8_t* rgb, uint8_t* has_rgb) {
     float X[3];
     mesh_position(g, i, j, k, X);
     float sum = 0.0f;
@@ -53,12 +53,11 @@ SFM_DEPTH_HD inline int32_t mesh_integrate_point(const MeshView* views, int32_t 
     for (int32_t v = 0; v < n_img; ++v) {
         const MeshView& V = views[v];
         if (!V.loaded) continue;
-        const float q[3] = {X[0] - V.C[0], X[1] - V.C[1], X[2] - V.C[2]};
-        const float h0 = depth_dot3(V.M, q), h1 = depth_dot3(V.M + 3, q), z = depth_dot3(V.M + 6, q);
+        float x, y, z;
+        project_point(V.M, V.C, X, &x, &y, &z);
         if (!(z > 0.0f)) continue;
-        const float x = floorf(h0 / z + 0.5f), y = floorf(h1 / z + 0.5f);
-        if (!(x >= 0.0f && x <= (float)(V.w - 1) && y >= 0.0f && y <= (float)(V.h - 1))) continue;
-        const int64_t idx = (int64_t)(int32_t)y * V.w + (int32_t)x;
+        const int64_t idx = nearest_pixel(x, y, V.w, V.h);
+        if (idx < 0) continue;
         const float d = depth[V.map_off + idx];
         if (!(d > 0.0f)) continue;
         const float sd = d - z;
@@ -67,16 +66,13 @@ SFM_DEPTH_HD inline int32_t mesh_integrate_point(const MeshView* views, int32_t 
         sum = sum + t;
         ++count;
         if (pixels && V.channels && fabsf(sd) <= trunc) {
-            const uint8_t* p = pixels + V.pix_off + idx * V.channels;
-            col[0] += p[0];
-            col[1] += V.channels == 3 ? p[1] : p[0];
-            col[2] += V.channels == 3 ? p[2] : p[0];
+            add_color(pixels + V.pix_off + idx * V.channels, V.channels, col);
             ++m;
         }
     }
     *tsdf = count > 0 ? sum / (float)count : 0.0f;
     if (pixels) {
-        for (int c = 0; c < 3; ++c) rgb[c] = m ? (uint8_t)((2u * col[c] + m) / (2u * m)) : (uint8_t)0;
+        for (int c = 0; c < 3; ++c) rgb[c] = m ? mean_u8(col[c], m) : (uint8_t)0;
         *has_rgb = m ? 1 : 0;
     }
     return count < 255 ? count : 255;
@@ -94,7 +90,7 @@ constexpr uint32_t mesh_pack_corners(int n) {
     return v;
 }
 constexpr uint32_t kMeshCorner1 = mesh_pack_corners(1), kMeshCorner2 = mesh_pack_corners(2);
-SFM_DEPTH_HD constexpr int mesh_tet_corner(int t, int n) {
+SFM_HD constexpr int mesh_tet_corner(int t, int n) {
     return n == 0 ? 0 : (n == 1 ? (int)((kMeshCorner1 >> (3 * t)) & 7u) : (n == 2 ? (int)((kMeshCorner2 >> (3 * t)) & 7u) : 7));
 }
 // An edge of a tetrahedron is (n << 2) | m over its corners n < m.  A case is the
@@ -169,8 +165,8 @@ static_assert(mesh_table_sound(mesh_make_table()), "the orientation rule decides
 
 // the slot of the owned edge along offset bits o (1 .. 7): x y z xy xz yz xyz
 // and back: 1 2 4 3 5 6 7 and 0 1 3 2 4 5 6, three bits an entry (plain integers again)
-SFM_DEPTH_HD constexpr int mesh_offset_of_slot(int s) { return (int)((0x1F5711u >> (3 * s)) & 7u); }
-SFM_DEPTH_HD constexpr int mesh_slot_of_offset(int o) { return (int)((0x1AC4C8u >> (3 * (o - 1))) & 7u); }
+SFM_HD constexpr int mesh_offset_of_slot(int s) { return (int)((0x1F5711u >> (3 * s)) & 7u); }
+SFM_HD constexpr int mesh_slot_of_offset(int o) { return (int)((0x1AC4C8u >> (3 * (o - 1))) & 7u); }
 constexpr bool mesh_slots_sound() {
     const int off[7] = {1, 2, 4, 3, 5, 6, 7};
     for (int s = 0; s < 7; ++s)
@@ -180,16 +176,16 @@ constexpr bool mesh_slots_sound() {
 static_assert(mesh_slots_sound(), "slots 0 .. 6 are the offsets x y z xy xz yz xyz");
 
 // ---- extraction -----------------------------------------------------------------------
-SFM_DEPTH_HD inline bool mesh_observed(const uint8_t* weight, int32_t min_weight, int64_t at) {
+SFM_HD inline bool mesh_observed(const uint8_t* weight, int32_t min_weight, int64_t at) {
     return (int32_t)weight[at] >= min_weight;
 }
 
 // The 7-bit mask of the owned edges of lattice point (i, j, k) that carry a
 // vertex, the triangles of its own cell (0 when the cell is not live) and how
 // many of them are degenerate.
-SFM_DEPTH_HD inline uint32_t mesh_point_marks(const MeshGrid& g, const float* tsdf, const uint8_t* weight,
-                                              int32_t min_weight, int32_t i, int32_t j, int32_t k, int32_t* n_tri,
-                                              int32_t* n_degenerate) {
+SFM_HD inline uint32_t mesh_point_marks(const MeshGrid& g, const float* tsdf, const uint8_t* weight,
+                                        int32_t min_weight, int32_t i, int32_t j, int32_t k, int32_t* n_tri,
+                                        int32_t* n_degenerate) {
     static constexpr MeshTable T = mesh_make_table();
     // bit (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1): that neighbour exists and is observed
     uint32_t obs = 0;
@@ -261,9 +257,9 @@ SFM_DEPTH_HD inline uint32_t mesh_point_marks(const MeshGrid& g, const float* ts
 }
 
 // The vertex on the owned edge `slot` of lattice point (i, j, k).  rgb_in NULL: no colours.
-SFM_DEPTH_HD inline void mesh_edge_vertex(const MeshGrid& g, const float* tsdf, const uint8_t* rgb_in,
-                                          const uint8_t* has_rgb, int32_t i, int32_t j, int32_t k, int slot, float* X,
-                                          uint8_t* rgb) {
+SFM_HD inline void mesh_edge_vertex(const MeshGrid& g, const float* tsdf, const uint8_t* rgb_in,
+                                    const uint8_t* has_rgb, int32_t i, int32_t j, int32_t k, int slot, float* X,
+                                    uint8_t* rgb) {
     const int o = mesh_offset_of_slot(slot);
     const int32_t bi = i + (o & 1), bj = j + ((o >> 1) & 1), bk = k + ((o >> 2) & 1);
     const int64_t a = mesh_raster(g, i, j, k), b = mesh_raster(g, bi, bj, bk);
@@ -283,8 +279,8 @@ SFM_DEPTH_HD inline void mesh_edge_vertex(const MeshGrid& g, const float* tsdf, 
 
 // The triangles of the live cell (i, j, k), written to tri (three indices each,
 // the cell's place in the output) in (tetrahedron, triangle) order; returns how many.
-SFM_DEPTH_HD inline int32_t mesh_cell_triangles(const MeshGrid& g, const float* tsdf, const int32_t* vert_base,
-                                                const uint8_t* mask, int32_t i, int32_t j, int32_t k, int32_t* tri) {
+SFM_HD inline int32_t mesh_cell_triangles(const MeshGrid& g, const float* tsdf, const int32_t* vert_base,
+                                          const uint8_t* mask, int32_t i, int32_t j, int32_t k, int32_t* tri) {
     static constexpr MeshTable T = mesh_make_table();
     uint32_t inside = 0;
     for (int c = 0; c < 8; ++c)

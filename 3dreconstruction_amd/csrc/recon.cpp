@@ -347,7 +347,6 @@ struct Log {
     }
 };
 
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
 struct Lap {   // adds the time since its construction to *acc
     double* acc;
     double t0;

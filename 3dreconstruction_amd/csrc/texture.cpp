@@ -1,9 +1,9 @@
 // Mesh texturing, host side (include/sfmcore.h, "Mesh texture"): the argument
-// checks, the atlas fit, the per-image matrices, the host twins (face views:
-// threads over chunks of faces, an atomic minimum per covered pixel; bake:
-// threads over rows of the atlas), the textured PLY writer and the entry points
-// over either backend.  The kernels and the transfers are texture.hip's.
-// SFM_DEPTHMAP_HOST_ONLY leaves the device entry points out
+// checks (the images': dense_views.cpp), the atlas fit, the host twins (face
+// views: threads over chunks of faces, an atomic minimum per covered pixel;
+// bake: threads over rows of the atlas), the textured PLY (dense_ply.cpp) and
+// the entry points over either backend.  The kernels and the transfers are
+// texture.hip's.  SFM_DEPTHMAP_HOST_ONLY leaves the device entry points out
 // (tests/cpp/texture_test.cpp).
 #pragma clang fp contract(off)
 
@@ -11,8 +11,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
+#include "dense_ply.h"
 #include "texture.h"
 
 using namespace sfm;
@@ -21,8 +23,6 @@ namespace {
 
 enum : int { kViews = 1, kBake = 2 };
 constexpr size_t kFaceChunk = 1024;   // faces a task of the host twin
-
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
 
 void atlas_fit(const char* who, int64_t n_triangles, int32_t cell, TexAtlas& A) {
     SFM_REQUIRE(n_triangles >= 0, SFM_ERR_INVALID_ARG, "%s: negative n_triangles", who);
@@ -58,49 +58,27 @@ void prepare(const char* who, int mode, int32_t n_img, const int32_t* wh, const 
     SFM_REQUIRE(n_vertices < ((int64_t)1 << 31), SFM_ERR_UNSUPPORTED, "%s: 2^31 vertices or more", who);
     atlas_fit(who, n_triangles, o.cell, P.atlas);
     std::memcpy(P.fill, o.fill, 3);
-    P.n_img = n_img;
     P.n_vertices = n_vertices;
     P.n_triangles = n_triangles;
+    dense_images_prepare(who, n_img, wh, channels, img_off, pixels, K, R, C, P.images);
     P.views.resize((size_t)n_img);
     const bool sample = (mode & kBake) != 0;
-    bool any = false;
     for (int32_t i = 0; i < n_img; ++i) {
-        const int32_t w = wh[2 * i], h = wh[2 * i + 1];
-        SFM_REQUIRE(w > 0 && h > 0, SFM_ERR_INVALID_ARG, "%s: image %d has a non-positive size", who, i);
-        SFM_REQUIRE((int64_t)w * h < ((int64_t)1 << 31), SFM_ERR_UNSUPPORTED, "%s: image %d has 2^31 or more pixels", who, i);
-        for (int a = 0; a < 9; ++a)
-            SFM_REQUIRE(std::isfinite(K[9 * i + a]) && std::isfinite(R[9 * i + a]) && std::isfinite(C[3 * i + a % 3]),
-                        SFM_ERR_INVALID_ARG, "%s: the camera of image %d is not finite", who, i);
+        const DenseImage& I = P.images.img[(size_t)i];
         TexView& T = P.views[(size_t)i];
         std::memset(&T, 0, sizeof T);
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) {
-                const double* k = K + 9 * i + 3 * r;
-                const double* rr = R + 9 * i + c;
-                T.M[3 * r + c] = (float)(k[0] * rr[0] + k[1] * rr[3] + k[2] * rr[6]);
-            }
-        for (int a = 0; a < 3; ++a) T.C[a] = (float)C[3 * i + a];
-        T.w = w;
-        T.h = h;
-        T.loaded = !pixels || img_off[i] >= 0;
-        if (T.loaded) P.max_pixels = std::max(P.max_pixels, (int64_t)w * h);
-        if (pixels && T.loaded) {
-            SFM_REQUIRE(channels[i] == 1 || channels[i] == 3, SFM_ERR_INVALID_ARG, "%s: image %d has %d channels", who, i,
-                        channels[i]);
-            T.channels = channels[i];
-            const int64_t lo = img_off[i], hi = img_off[i] + (int64_t)w * h * channels[i];
-            P.pool_lo = any ? std::min(P.pool_lo, lo) : lo;
-            P.pool_hi = any ? std::max(P.pool_hi, hi) : hi;
-            any = true;
-        }
+        dense_KR(K, R, i, T.M);
+        dense_C(C, i, T.C);
+        T.w = I.w;
+        T.h = I.h;
+        T.channels = I.channels;
+        T.loaded = I.loaded;
+        T.pix_off = I.pix_off;
+        if (T.loaded) P.max_pixels = std::max(P.max_pixels, (int64_t)T.w * T.h);
     }
-    // the colour bytes are uploaded from pool_lo on
-    for (int32_t i = 0; i < n_img; ++i) P.views[(size_t)i].pix_off = P.views[(size_t)i].channels ? img_off[i] - P.pool_lo : 0;
     for (int64_t k = 0; k < 3 * n_vertices; ++k)
         SFM_REQUIRE(std::isfinite(V[k]), SFM_ERR_INVALID_ARG, "%s: vertex %lld is not finite", who, (long long)(k / 3));
-    for (int64_t k = 0; k < 3 * n_triangles; ++k)
-        SFM_REQUIRE(tri[k] >= 0 && tri[k] < n_vertices, SFM_ERR_INVALID_ARG, "%s: triangle %lld names vertex %d of %lld", who,
-                    (long long)(k / 3), tri[k], (long long)n_vertices);
+    require_triangles(who, n_triangles, tri, n_vertices);
     if (face_view)
         for (int64_t f = 0; f < n_triangles; ++f) {
             const int32_t v = face_view[f];
@@ -112,7 +90,7 @@ void prepare(const char* who, int mode, int32_t n_img, const int32_t* wh, const 
     int64_t bytes = (int64_t)(P.views.size() * sizeof(TexView)) + 12 * n_vertices + 24 * n_triangles;
     if (mode & kViews) bytes += 8 * P.max_pixels;
     if (sample)
-        bytes += (P.pool_hi - P.pool_lo) + (vertex_rgb ? 3 * n_vertices : 0) + 3 * (int64_t)P.atlas.W * P.atlas.H + 24 * n_triangles;
+        bytes += (P.images.pool_hi - P.images.pool_lo) + (vertex_rgb ? 3 * n_vertices : 0) + 3 * (int64_t)P.atlas.W * P.atlas.H + 24 * n_triangles;
     *resident_bytes = bytes;
     const int64_t budget = o.device_bytes > 0 ? o.device_bytes : kTexDefaultDeviceBytes;
     SFM_REQUIRE(bytes <= budget, SFM_ERR_UNSUPPORTED,
@@ -134,11 +112,11 @@ void face_views_host(const TexProblem& P, const float* V, const int32_t* tri, in
     std::fill(face_pixels, face_pixels + n, 0);
     std::vector<uint64_t> id((size_t)P.max_pixels);
     std::vector<int64_t> refused(chunks, 0);
-    for (int32_t v = 0; v < P.n_img; ++v) {
+    for (int32_t v = 0; v < P.images.n_img; ++v) {
         const TexView& T = P.views[(size_t)v];
         if (!T.loaded) continue;
         std::fill(id.begin(), id.begin() + (size_t)T.w * T.h, ~(uint64_t)0);
-        depth_parallel_for(chunks, [&](size_t c) {
+        dense_parallel_for(chunks, [&](size_t c) {
             for (size_t f = c * kFaceChunk; f < std::min(n, (c + 1) * kFaceChunk); ++f) {
                 TexFace F;
                 if (!tex_face_setup(T, V, tri, (int64_t)f, F)) {
@@ -153,7 +131,7 @@ void face_views_host(const TexProblem& P, const float* V, const int32_t* tri, in
                     }
             }
         });
-        depth_parallel_for(chunks, [&](size_t c) {
+        dense_parallel_for(chunks, [&](size_t c) {
             for (size_t f = c * kFaceChunk; f < std::min(n, (c + 1) * kFaceChunk); ++f) {
                 TexFace F;
                 if (!tex_face_setup(T, V, tri, (int64_t)f, F) || !F.box()) continue;
@@ -181,7 +159,7 @@ void bake_host(const TexProblem& P, const uint8_t* pixels, const float* V, const
                const int32_t* face_view, uint8_t* texture, float* uv) {
     const TexAtlas& A = P.atlas;
     const uint32_t fill = tex_pack(P.fill);
-    depth_parallel_for((size_t)A.H, [&](size_t row) {
+    dense_parallel_for((size_t)A.H, [&](size_t row) {
         const int32_t ty = (int32_t)row;
         for (int32_t tx = 0; tx < A.W; ++tx) {
             uint8_t* out = texture + 3 * ((size_t)ty * A.W + tx);
@@ -251,7 +229,7 @@ int bake(const char* who, sfm_ctx* ctx, bool device, int32_t n_img, const int32_
 #endif
         } else {
             const double t0 = seconds_now();
-            bake_host(P, pixels ? pixels + P.pool_lo : nullptr, V, vertex_rgb, tri, face_view, texture, uv);
+            bake_host(P, pixels ? pixels + P.images.pool_lo : nullptr, V, vertex_rgb, tri, face_view, texture, uv);
             st.seconds[1] = seconds_now() - t0;
         }
     }
@@ -353,34 +331,19 @@ extern "C" int sfm_mesh_write_textured_ply(const char* path, const char* texture
                         (n_triangles == 0 || (tri && uv)),
                     SFM_ERR_INVALID_ARG, "%s: null path, name, V, tri or uv, or a negative count", who);
         SFM_REQUIRE(!std::strpbrk(texture_name, "\r\n"), SFM_ERR_INVALID_ARG, "%s: the texture's name holds a line break", who);
-        for (int64_t k = 0; k < 3 * n_triangles; ++k)
-            SFM_REQUIRE(tri[k] >= 0 && tri[k] < n_vertices, SFM_ERR_INVALID_ARG, "%s: triangle %lld names vertex %d of %lld",
-                        who, (long long)(k / 3), tri[k], (long long)n_vertices);
-        std::FILE* f = std::fopen(path, "wb");
-        SFM_REQUIRE(f, SFM_ERR_INVALID_ARG, "%s: cannot open %s for writing", who, path);
-        std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment TextureFile %s\nelement vertex %lld\n", texture_name,
-                     (long long)n_vertices);
-        std::fprintf(f, "property float x\nproperty float y\nproperty float z\n");
-        std::fprintf(f, "element face %lld\nproperty list uchar int vertex_indices\nproperty list uchar float texcoord\nend_header\n",
-                     (long long)n_triangles);
-        if (n_vertices) std::fwrite(V, 12, (size_t)n_vertices, f);
-        std::vector<uint8_t> buf((size_t)38 * 4096);
-        for (int64_t k0 = 0; k0 < n_triangles; k0 += 4096) {
-            const int64_t k1 = std::min<int64_t>(k0 + 4096, n_triangles);
-            uint8_t* p = buf.data();
-            for (int64_t k = k0; k < k1; ++k) {
-                *p++ = 3;
-                std::memcpy(p, tri + 3 * k, 12);
-                p += 12;
-                *p++ = 6;
-                std::memcpy(p, uv + 6 * k, 24);
-                p += 24;
-            }
-            std::fwrite(buf.data(), 1, (size_t)(p - buf.data()), f);
-        }
-        const bool bad = std::ferror(f) != 0;
-        const bool closed = std::fclose(f) == 0;
-        SFM_REQUIRE(!bad && closed, SFM_ERR_INVALID_ARG, "%s: writing %s failed", who, path);
+        require_triangles(who, n_triangles, tri, n_vertices);
+        PlyWriter ply(who, path,
+                      std::string("comment TextureFile ") + texture_name + "\nelement vertex " + std::to_string(n_vertices) +
+                          "\nproperty float x\nproperty float y\nproperty float z\nelement face " + std::to_string(n_triangles) +
+                          "\nproperty list uchar int vertex_indices\nproperty list uchar float texcoord\n");
+        ply.records(n_vertices, 12, [&](int64_t k, uint8_t* p) { std::memcpy(p, V + 3 * k, 12); });
+        ply.records(n_triangles, 38, [&](int64_t k, uint8_t* p) {
+            p[0] = 3;
+            std::memcpy(p + 1, tri + 3 * k, 12);
+            p[13] = 6;
+            std::memcpy(p + 14, uv + 6 * k, 24);
+        });
+        ply.close();
         return (int)SFM_OK;
     });
 }

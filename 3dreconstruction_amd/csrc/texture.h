@@ -1,11 +1,11 @@
 // Mesh texturing (include/sfmcore.h, "Mesh texture"): what texture.cpp (host:
-// checks, the atlas fit, the host twins, the PLY writer) and texture.hip (the
+// checks, the atlas fit, the host twins, the textured PLY) and texture.hip (the
 // kernels and the launches) share.
 #pragma once
 #include <cstdint>
 #include <vector>
 
-#include "depthmap.h"
+#include "dense_views.h"
 #include "texture_point.h"
 
 namespace sfm {
@@ -15,9 +15,8 @@ constexpr int64_t kTexDefaultDeviceBytes = (int64_t)4 << 30;
 
 // What a call works on, checked and precomputed on the host (texture.cpp).
 struct TexProblem {
-    int32_t n_img = 0;
+    DenseImages images;                 // sizes, the colour pool's window
     std::vector<TexView> views;         // [n_img]
-    int64_t pool_lo = 0, pool_hi = 0;   // the bytes of the colour pool that loaded images cover
     int64_t max_pixels = 0;             // of the largest loaded image
     int64_t n_vertices = 0, n_triangles = 0;
     TexAtlas atlas{};

@@ -202,22 +202,6 @@ __global__ __launch_bounds__(kTexBlock) void tex_uv_kernel(BakeLaunch a) {
     for (int k = 0; k < 6; ++k) a.uv[6 * f + k] = uv[k];
 }
 
-struct Events {
-    hipEvent_t ev[4] = {};
-    Events() {
-        for (hipEvent_t& e : ev) SFM_HIP(hipEventCreate(&e));
-    }
-    ~Events() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    double between(int p, int q) const {
-        float ms = 0.f;
-        SFM_HIP(hipEventElapsedTime(&ms, ev[p], ev[q]));
-        return ms * 1e-3;
-    }
-};
-
 // the mesh and the views of a call on the device
 struct Resident {
     DBuf<TexView> views;
@@ -241,8 +225,8 @@ void upload_mesh(hipStream_t s, const TexProblem& P, const float* V, const int32
 }
 
 void upload_images(hipStream_t s, const TexProblem& P, const uint8_t* pixels, const uint8_t* vertex_rgb, Resident& r) {
-    r.pool.alloc((size_t)std::max<int64_t>(P.pool_hi - P.pool_lo, 1));
-    if (pixels) r.pool.upload(pixels + P.pool_lo, (size_t)(P.pool_hi - P.pool_lo), s);
+    r.pool.alloc((size_t)std::max<int64_t>(P.images.pool_hi - P.images.pool_lo, 1));
+    if (pixels) r.pool.upload(pixels + P.images.pool_lo, (size_t)(P.images.pool_hi - P.images.pool_lo), s);
     if (vertex_rgb) {
         r.vrgb.alloc(3 * (size_t)P.n_vertices);
         r.vrgb.upload(vertex_rgb, 3 * (size_t)P.n_vertices, s);
@@ -271,7 +255,7 @@ void launch_views(hipStream_t s, const TexProblem& P, Resident& r) {
     a.counters = r.counters.p;
     a.n_triangles = P.n_triangles;
     const dim3 faces(blocks(P.n_triangles)), big(kTexBigGroups), wg(kTexBlock);
-    for (int32_t v = 0; v < P.n_img; ++v) {
+    for (int32_t v = 0; v < P.images.n_img; ++v) {
         const TexView& T = P.views[(size_t)v];
         if (!T.loaded) continue;
         a.view = v;
@@ -335,14 +319,14 @@ void tex_face_views_device(sfm_ctx* ctx, const TexProblem& P, const float* V, co
     CtxScope scope_(ctx);
     hipStream_t s = ctx->stream;
     Resident r;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     upload_mesh(s, P, V, tri, r);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     launch_views(s, P, r);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     download_views(s, P, r, face_view, face_pixels);
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     read_counts(s, P, r, st);
     for (int p = 0; p < 3; ++p) st->seconds[p] = ev.between(p, p + 1);
 }
@@ -352,16 +336,16 @@ void tex_bake_device(sfm_ctx* ctx, const TexProblem& P, const uint8_t* pixels, c
     CtxScope scope_(ctx);
     hipStream_t s = ctx->stream;
     Resident r;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     upload_mesh(s, P, V, tri, r);
     upload_images(s, P, pixels, vertex_rgb, r);
     r.face_view.upload(face_view, (size_t)P.n_triangles, s);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     launch_bake(s, P, r);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     download_bake(s, P, r, texture, uv);
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     SFM_HIP(hipStreamSynchronize(s));
     for (int p = 0; p < 3; ++p) st->seconds[p] = ev.between(p, p + 1);
 }
@@ -372,17 +356,17 @@ void tex_texture_device(sfm_ctx* ctx, const TexProblem& P, const uint8_t* pixels
     CtxScope scope_(ctx);
     hipStream_t s = ctx->stream;
     Resident r;
-    Events ev;
-    SFM_HIP(hipEventRecord(ev.ev[0], s));
+    StreamEvents<4> ev;
+    ev.record(0, s);
     upload_mesh(s, P, V, tri, r);
     upload_images(s, P, pixels, vertex_rgb, r);
-    SFM_HIP(hipEventRecord(ev.ev[1], s));
+    ev.record(1, s);
     launch_views(s, P, r);
     launch_bake(s, P, r);
-    SFM_HIP(hipEventRecord(ev.ev[2], s));
+    ev.record(2, s);
     download_views(s, P, r, face_view, face_pixels);
     download_bake(s, P, r, texture, uv);
-    SFM_HIP(hipEventRecord(ev.ev[3], s));
+    ev.record(3, s);
     read_counts(s, P, r, &st->views);
     for (int p = 0; p < 3; ++p) st->seconds[p] = ev.between(p, p + 1);
 }

@@ -10,7 +10,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "depthmap_point.h"
+#include "dense_common.h"
 
 namespace sfm {
 
@@ -41,8 +41,8 @@ struct TexAtlas {
     int32_t s, cols, W, H;
 };
 
-SFM_DEPTH_HD inline int64_t tex_floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-SFM_DEPTH_HD inline int64_t tex_ceil_div(int64_t a, int64_t b) { return -tex_floor_div(-a, b); }
+SFM_HD inline int64_t tex_floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+SFM_HD inline int64_t tex_ceil_div(int64_t a, int64_t b) { return -tex_floor_div(-a, b); }
 
 // ---- a face in a view (steps a, b) ----------------------------------------------------
 struct TexFace {
@@ -51,23 +51,19 @@ struct TexFace {
     int64_t A2;           // twice the area, after the exchange; 0: covers nothing
     int32_t px0, px1, py0, py1;   // the bounding box clipped to the image, inclusive; empty when px0 > px1 or py0 > py1
     bool inside, front;   // the unrounded projections lie in the image; the face looks at the camera
-    SFM_DEPTH_HD int64_t box() const {
+    SFM_HD int64_t box() const {
         return A2 > 0 && px0 <= px1 && py0 <= py1 ? (int64_t)(px1 - px0 + 1) * (py1 - py0 + 1) : 0;
     }
 };
 
 // false: the face is not drawable in the view
-SFM_DEPTH_HD inline bool tex_face_setup(const TexView& v, const float* V, const int32_t* tri, int64_t f, TexFace& F) {
+SFM_HD inline bool tex_face_setup(const TexView& v, const float* V, const int32_t* tri, int64_t f, TexFace& F) {
     float x[3], y[3], z[3];
     const float* P[3];
     bool ok = true;
     for (int k = 0; k < 3; ++k) {
         P[k] = V + 3 * (int64_t)tri[3 * f + k];
-        const float q[3] = {P[k][0] - v.C[0], P[k][1] - v.C[1], P[k][2] - v.C[2]};
-        const float h0 = depth_dot3(v.M, q), h1 = depth_dot3(v.M + 3, q);
-        z[k] = depth_dot3(v.M + 6, q);
-        x[k] = h0 / z[k];
-        y[k] = h1 / z[k];
+        project_point(v.M, v.C, P[k], &x[k], &y[k], &z[k]);
         ok = ok && z[k] > 0.0f && fabsf(x[k]) <= kTexMaxCoord && fabsf(y[k]) <= kTexMaxCoord;
     }
     if (!ok) return false;
@@ -82,7 +78,7 @@ SFM_DEPTH_HD inline bool tex_face_setup(const TexView& v, const float* V, const 
     const float e2[3] = {P[2][0] - P[0][0], P[2][1] - P[0][1], P[2][2] - P[0][2]};
     const float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
     const float t[3] = {v.C[0] - P[0][0], v.C[1] - P[0][1], v.C[2] - P[0][2]};
-    F.front = depth_dot3(n, t) > 0.0f;
+    F.front = dot3(n, t) > 0.0f;
     F.A2 = (F.X[1] - F.X[0]) * (F.Y[2] - F.Y[0]) - (F.X[2] - F.X[0]) * (F.Y[1] - F.Y[0]);
     if (F.A2 < 0) {
         const int64_t tx = F.X[1], ty = F.Y[1];
@@ -108,7 +104,7 @@ SFM_DEPTH_HD inline bool tex_face_setup(const TexView& v, const float* V, const 
 }
 
 // Is the centre of pixel (px, py) covered?  *key: ((uint64)bits(d) << 32) | face.
-SFM_DEPTH_HD inline bool tex_pixel(const TexFace& F, uint32_t face, int32_t px, int32_t py, uint64_t* key) {
+SFM_HD inline bool tex_pixel(const TexFace& F, uint32_t face, int32_t px, int32_t py, uint64_t* key) {
     const int64_t Px = (int64_t)kTexSub * px, Py = (int64_t)kTexSub * py;
     int64_t E[3];
     for (int k = 0; k < 3; ++k) {
@@ -126,8 +122,8 @@ SFM_DEPTH_HD inline bool tex_pixel(const TexFace& F, uint32_t face, int32_t px, 
 }
 
 // step d for one (face, view): the running best of the face
-SFM_DEPTH_HD inline void tex_score(const TexFace& F, bool drawable, int64_t covered, int64_t won, int32_t view,
-                                   int32_t* best_view, int32_t* best_pixels) {
+SFM_HD inline void tex_score(const TexFace& F, bool drawable, int64_t covered, int64_t won, int32_t view,
+                             int32_t* best_view, int32_t* best_pixels) {
     if (drawable && F.front && F.inside && covered >= 1 && won == covered && covered > (int64_t)*best_pixels) {
         *best_view = view;
         *best_pixels = (int32_t)covered;
@@ -136,7 +132,7 @@ SFM_DEPTH_HD inline void tex_score(const TexFace& F, bool drawable, int64_t cove
 
 // ---- the atlas ------------------------------------------------------------------------
 // the corner k of face f in texel units from the atlas's origin
-SFM_DEPTH_HD inline void tex_corner(const TexAtlas& A, int64_t f, int k, float* cx, float* cy) {
+SFM_HD inline void tex_corner(const TexAtlas& A, int64_t f, int k, float* cx, float* cy) {
     const int64_t sq = f / 2;
     const float ox = (float)((int32_t)(sq % A.cols) * A.s), oy = (float)((int32_t)(sq / A.cols) * A.s);
     const float s = (float)A.s;
@@ -151,7 +147,7 @@ SFM_DEPTH_HD inline void tex_corner(const TexAtlas& A, int64_t f, int k, float* 
     *cx = ox + x;
     *cy = oy + y;
 }
-SFM_DEPTH_HD inline void tex_uv(const TexAtlas& A, int64_t f, float* uv) {
+SFM_HD inline void tex_uv(const TexAtlas& A, int64_t f, float* uv) {
     for (int k = 0; k < 3; ++k) {
         float cx, cy;
         tex_corner(A, f, k, &cx, &cy);
@@ -160,15 +156,15 @@ SFM_DEPTH_HD inline void tex_uv(const TexAtlas& A, int64_t f, float* uv) {
     }
 }
 
-SFM_DEPTH_HD inline uint8_t tex_round(float v) { return (uint8_t)floorf(v + 0.5f); }
+SFM_HD inline uint8_t tex_round(float v) { return (uint8_t)floorf(v + 0.5f); }
 // a texel as r | g << 8 | b << 16 (registers on the device; the host twin unpacks)
-SFM_DEPTH_HD inline uint32_t tex_pack(const uint8_t* c) { return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16; }
-SFM_DEPTH_HD inline void tex_unpack(uint32_t rgb, uint8_t* c) {
+SFM_HD inline uint32_t tex_pack(const uint8_t* c) { return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16; }
+SFM_HD inline void tex_unpack(uint32_t rgb, uint8_t* c) {
     c[0] = (uint8_t)rgb, c[1] = (uint8_t)(rgb >> 8), c[2] = (uint8_t)(rgb >> 16);
 }
 
 // the face of texel (tx, ty), or -1, and its barycentric weights
-SFM_DEPTH_HD inline int64_t tex_texel_face(const TexAtlas& A, int64_t n_triangles, int32_t tx, int32_t ty, float* l1, float* l2) {
+SFM_HD inline int64_t tex_texel_face(const TexAtlas& A, int64_t n_triangles, int32_t tx, int32_t ty, float* l1, float* l2) {
     const int32_t a = tx % A.s, b = ty % A.s;
     const int64_t sq = (int64_t)(ty / A.s) * A.cols + tx / A.s;
     const int half = a + b <= A.s - 2 ? 0 : 1;
@@ -181,37 +177,23 @@ SFM_DEPTH_HD inline int64_t tex_texel_face(const TexAtlas& A, int64_t n_triangle
 }
 
 // a texel of a face textured from view v
-SFM_DEPTH_HD inline uint32_t tex_sample(const TexView& v, const uint8_t* pixels, const float* V, const int32_t* tri, int64_t f,
-                                        float l1, float l2, uint32_t fill) {
+SFM_HD inline uint32_t tex_sample(const TexView& v, const uint8_t* pixels, const float* V, const int32_t* tri, int64_t f,
+                                  float l1, float l2, uint32_t fill) {
     const float *P0 = V + 3 * (int64_t)tri[3 * f], *P1 = V + 3 * (int64_t)tri[3 * f + 1], *P2 = V + 3 * (int64_t)tri[3 * f + 2];
-    float q[3];
-    for (int c = 0; c < 3; ++c) {
-        const float p = (P0[c] + l1 * (P1[c] - P0[c])) + l2 * (P2[c] - P0[c]);
-        q[c] = p - v.C[c];
-    }
-    const float h0 = depth_dot3(v.M, q), h1 = depth_dot3(v.M + 3, q), z = depth_dot3(v.M + 6, q);
+    float X[3], px, py, z;
+    for (int c = 0; c < 3; ++c) X[c] = (P0[c] + l1 * (P1[c] - P0[c])) + l2 * (P2[c] - P0[c]);
+    project_point(v.M, v.C, X, &px, &py, &z);
     if (!(z > 0.0f)) return fill;
-    const float x = fminf(fmaxf(h0 / z, 0.0f), (float)(v.w - 1)), y = fminf(fmaxf(h1 / z, 0.0f), (float)(v.h - 1));
-    const float fx = floorf(x), fy = floorf(y), dx = x - fx, dy = y - fy;
-    const int32_t gx = (int32_t)fx, gy = (int32_t)fy;
-    const int32_t gx1 = gx + 1 < v.w - 1 ? gx + 1 : v.w - 1, gy1 = gy + 1 < v.h - 1 ? gy + 1 : v.h - 1;
-    const int32_t ch = v.channels;
-    const uint8_t* img = pixels + v.pix_off;
-    const uint8_t *r00 = img + ((int64_t)gy * v.w + gx) * ch, *r10 = img + ((int64_t)gy * v.w + gx1) * ch;
-    const uint8_t *r01 = img + ((int64_t)gy1 * v.w + gx) * ch, *r11 = img + ((int64_t)gy1 * v.w + gx1) * ch;
+    const float x = fminf(fmaxf(px, 0.0f), (float)(v.w - 1)), y = fminf(fmaxf(py, 0.0f), (float)(v.h - 1));
     uint32_t rgb = 0;
-    for (int c = 0; c < 3; ++c) {
-        const int o = ch == 3 ? c : 0;
-        const float p00 = (float)r00[o], p10 = (float)r10[o], p01 = (float)r01[o], p11 = (float)r11[o];
-        const float top = p00 + dx * (p10 - p00), bot = p01 + dx * (p11 - p01);
-        rgb |= (uint32_t)tex_round(top + dy * (bot - top)) << (8 * c);
-    }
+    for (int c = 0; c < 3; ++c)
+        rgb |= (uint32_t)tex_round(bilinear_u8(pixels + v.pix_off, v.w, v.h, v.channels, v.channels == 3 ? c : 0, x, y)) << (8 * c);
     return rgb;
 }
 
 // a texel of a face without a view: the vertex colours, or the fill
-SFM_DEPTH_HD inline uint32_t tex_fallback(const uint8_t* vertex_rgb, const int32_t* tri, int64_t f, float l1, float l2,
-                                          uint32_t fill) {
+SFM_HD inline uint32_t tex_fallback(const uint8_t* vertex_rgb, const int32_t* tri, int64_t f, float l1, float l2,
+                                    uint32_t fill) {
     if (!vertex_rgb) return fill;
     const uint8_t *c0 = vertex_rgb + 3 * (int64_t)tri[3 * f], *c1 = vertex_rgb + 3 * (int64_t)tri[3 * f + 1],
                   *c2 = vertex_rgb + 3 * (int64_t)tri[3 * f + 2];

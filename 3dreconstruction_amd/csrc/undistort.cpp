@@ -21,8 +21,6 @@ using namespace sfm;
 
 namespace {
 
-double seconds_now() { return PhaseTimer::now() * 1e-3; }
-
 // doubles per intrinsics block (sfm_ba_intr_width, which lives with the planner)
 int intr_width(int32_t cm) { return cm == SFM_CAM_RADIAL3 ? 6 : (cm == SFM_CAM_PINHOLE || cm == SFM_CAM_SNAVELY ? 4 : 0); }
 

@@ -111,44 +111,47 @@ tests/cpp/undistort_test: tests/cpp/undistort_test.cpp $(UNDISTORT_HOST_SRCS) $(
 	    -I/opt/rocm/include -o $@ $< $(UNDISTORT_HOST_SRCS) -lpthread
 
 # the dense depth maps on the host backend: the host paths of csrc/depthmap.cpp
-# (checks, view selection, the host twins of the estimation and of the filter)
-# and csrc/dense_scene.cpp and the façade of include/sfm/dense.hpp compiled in
+# (checks, view selection, the host twins of the estimation and of the filter),
+# csrc/dense_views.cpp (the images' checks, the thread pool) and
+# csrc/dense_scene.cpp and the façade of include/sfm/dense.hpp compiled in
 # (no library, no HIP runtime: host only).
 # DEPTHMAP_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
-DEPTHMAP_HOST_SRCS := $(CSRC)/depthmap.cpp $(CSRC)/undistort.cpp $(CSRC)/dense_scene.cpp
+DEPTHMAP_HOST_SRCS := $(CSRC)/depthmap.cpp $(CSRC)/dense_views.cpp $(CSRC)/undistort.cpp $(CSRC)/dense_scene.cpp
 tests/cpp/depthmap_test: tests/cpp/depthmap_test.cpp $(DEPTHMAP_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas $(DEPTHMAP_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY -DSFM_UNDISTORT_HOST_ONLY \
 	    -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(DEPTHMAP_HOST_SRCS) -lpthread
 
 # the dense fusion on the host backend: the host paths of csrc/fuse.cpp (checks,
-# pair lists, the host twin, the view lists, the PLY writer, sfm_densify_host)
-# over those of the depth maps, and the façade of include/sfm/dense.hpp compiled
+# pair lists, the host twin, the view lists, sfm_densify_host) and
+# csrc/dense_ply.cpp (the PLY writer) over those of the depth maps, and the façade of include/sfm/dense.hpp compiled
 # in (no library, no HIP runtime: host only).  fuse.cpp and depthmap.cpp switch
 # contraction off themselves (#pragma at their top), as the .hip files do.
 # DEPTHFUSE_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
-DEPTHFUSE_HOST_SRCS := $(CSRC)/fuse.cpp $(DEPTHMAP_HOST_SRCS)
+DEPTHFUSE_HOST_SRCS := $(CSRC)/fuse.cpp $(CSRC)/dense_ply.cpp $(DEPTHMAP_HOST_SRCS)
 tests/cpp/depthfuse_test: tests/cpp/depthfuse_test.cpp $(DEPTHFUSE_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(DEPTHFUSE_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY \
 	    -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(DEPTHFUSE_HOST_SRCS) -lpthread
 
 # the mesh stage on the host backend: the host paths of csrc/mesh.cpp (checks,
-# the grid fit, the host twins of the integration and the extraction, the PLY
-# writer) over those of the depth maps (its thread pool), and the façade of
-# include/sfm/mesh.hpp compiled in (no library, no HIP runtime: host only).
+# the grid fit, the host twins of the integration and the extraction),
+# csrc/dense_views.cpp (the images' checks, the thread pool) and
+# csrc/dense_ply.cpp (the PLY writer), and the façade of include/sfm/mesh.hpp
+# compiled in (no library, no HIP runtime: host only).
 # mesh.cpp switches contraction off itself (#pragma at its top), as mesh.hip does.
 # MESH_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
-MESH_HOST_SRCS := $(CSRC)/mesh.cpp $(DEPTHMAP_HOST_SRCS)
+MESH_HOST_SRCS := $(CSRC)/mesh.cpp $(CSRC)/dense_views.cpp $(CSRC)/dense_ply.cpp
 tests/cpp/mesh_test: tests/cpp/mesh_test.cpp $(MESH_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(MESH_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY \
 	    -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(MESH_HOST_SRCS) -lpthread
 
 # the mesh texturing on the host backend: the host paths of csrc/texture.cpp
-# (checks, the atlas fit, the host twins of the view choice and the bake, the
-# textured PLY writer) over those of the mesh stage and the depth maps (its
-# thread pool), and the façade of include/sfm/mesh.hpp compiled in (no library,
-# no HIP runtime: host only).  texture.cpp switches contraction off itself.
+# (checks, the atlas fit, the host twins of the view choice and the bake),
+# csrc/dense_views.cpp and csrc/dense_ply.cpp as the mesh stage's test,
+# csrc/undistort.cpp (sfm::TexturedMesh::write stores the atlas with its PNM
+# writer), and the façade of include/sfm/mesh.hpp compiled in (no library, no
+# HIP runtime: host only).  texture.cpp switches contraction off itself.
 # TEXTURE_TEST_FLAGS=-fsanitize=address,undefined gives the sanitizer build.
-TEXTURE_HOST_SRCS := $(CSRC)/texture.cpp $(MESH_HOST_SRCS)
+TEXTURE_HOST_SRCS := $(CSRC)/texture.cpp $(CSRC)/dense_views.cpp $(CSRC)/dense_ply.cpp $(CSRC)/undistort.cpp
 tests/cpp/texture_test: tests/cpp/texture_test.cpp $(TEXTURE_HOST_SRCS) $(HDRS)
 	g++ -O2 -std=c++17 -Wall -Wno-unknown-pragmas -ffp-contract=off $(TEXTURE_TEST_FLAGS) -DSFM_DEPTHMAP_HOST_ONLY \
 	    -DSFM_UNDISTORT_HOST_ONLY -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(TEXTURE_HOST_SRCS) -lpthread
